@@ -6,8 +6,8 @@ Workload (BASELINE.json configs[1]): srncar.json network (3 shape blocks,
 accumulation -- by default the bf16x3f plan: the forward chains carry every
 weight and activation as a bf16 hi + lo pair (three bf16 MFMAs per block:
 rendered rgb within 1e-4 of the fp32 reference, the north-star bar), the
-backward runs on bf16 operands; bf16, bf16x3 and fp32 are measured in the same
-line (``precisions``) -- synthetic SRN-cars-like data (targets ray-cast from an
+backward runs on bf16 operands; with --full bf16, bf16x3 and fp32 are measured
+in the same line (``precisions``) -- synthetic SRN-cars-like data (targets ray-cast from an
 ellipsoid object by the SRN-format generator's renderer, cameras on a
 radius-1.3 sphere, focal 131.25, near/far 0.8/1.8; no dataset is available
 offline; --config c3 uses the srnchair.json geometry: near/far 1.25/2.75,
@@ -19,7 +19,16 @@ layers, code rows) -> [RCCL all-reduce of the gradients when N > 1] -> AdamW
 over the model and both code tables.  ``value`` = ray-samples of all ranks /
 max-over-ranks wall time of the K timed steps.
 
-Run:  python bench.py [--gpus N --steps K --warmup W]
+A plain run does what that figure needs and no more: set-up, W warm-up steps,
+the K timed steps, the result line (metric, value, unit, ms_per_step, ...).
+--dump-outputs DIR also writes what the last timed step returned (and the
+state it left) as DIR/<name>.npy: the inputs are seeded, so two builds run
+with the same arguments compare array for array.  --full adds everything else
+the line can carry: the per-kernel timers of the timed steps and their
+rooflines, the box's clock probe, the other precisions of the same step and
+the CPU baseline.
+
+Run:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
       (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py)
 """
 import argparse
@@ -73,7 +82,7 @@ def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=int(os.environ.get("WORLD_SIZE", "1")))
     ap.add_argument("--steps", type=int, default=50)
@@ -97,13 +106,21 @@ def parse():
     #   c4eval: optimize.py's evaluation loop (src/optimizer.py:108-130): one
     #       step = one 128^2 view x 64 samples rendered forward-only + MSE
     ap.add_argument("--config", default="c2", choices=["c2", "c3", "c4", "c4eval", "c5"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (losses, rendered rgb) and "
+                         "the state it left (model parameters, code tables) as DIR/<name>.npy (float32; an array "
+                         "beyond its share of 64 MB as a fixed seeded sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel timers and rooflines, the "
+                         "clock probe, the other precisions of the step, the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-overlap", action="store_true",
                     help="one dX launch then one dW launch (no two-stream dX / dW pipelining)")
     ap.add_argument("--bwd-ranges", type=int, default=None, help="row ranges of the dX / dW pipeline")
     ap.add_argument("--dw-side-wgs", type=int, default=None,
                     help="persistent workgroups of the dW launches that run beside a dX chain (0: 256)")
-    ap.add_argument("--no-fp32", action="store_true", help="skip the secondary precisions' figures of the C2 step")
+    ap.add_argument("--no-fp32", action="store_true",
+                    help="with --full: skip the secondary precisions' figures of the C2 step")
     ap.add_argument("--recompute", action="store_true",
                     help="store-vs-recompute A/B: loss forwards store masks only, a second forward writes the dW planes")
     ap.add_argument("--cpu-baseline-only", type=int, default=None, help=argparse.SUPPRESS)
@@ -113,7 +130,10 @@ def parse():
     # rehearsal of the N > 1 path on a one-GPU box: gloo, every rank on cuda:0
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--one-device", action="store_true")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def make_pose(radius, az_deg, el_deg):
@@ -278,11 +298,15 @@ def build_workload(args, dev, rank, world, precision, timers, dist):
             views = []
             for v in range(n_views):
                 ro, vd = _eng.get_rays_dev(H, W, focal, True, poses[v])
-                loss, _, _ = img.forward_backward(ro, vd, core.stratified_z(dev), gts[v], sc1, tc1, 0,
-                                                  weight_grads=False)
+                loss, rgb, _ = img.forward_backward(ro, vd, core.stratified_z(dev), gts[v], sc1, tc1, 0,
+                                                    weight_grads=False)
                 views.append(loss)
             copt.step()
             last["losses"] = torch.cat(views)
+            last["out"] = {"losses": last["losses"], "rgb": rgb}
+
+        def state():
+            return {"shape_code": sc1, "texture_code": tc1}
     elif args.config == "c4eval":
         # src/optimizer.py:108-130: no_grad forward of a held-out view with
         # the optimised codes, composite, MSE (PSNR); the view rays come from
@@ -305,14 +329,27 @@ def build_workload(args, dev, rank, world, precision, timers, dist):
             timers.done("fwd", ev, n=M)
             rgb, _ = _eng.composite_fwd(sig, rgbs, z, R, args.n_coarse)
             last["losses"] = ((rgb - gts[v]) ** 2).mean().reshape(1)
+            last["out"] = {"losses": last["losses"], "rgb": rgb}
+
+        def state():
+            return {}                  # forward only: the step leaves no state
     else:
         def step(i):
             v = i % n_views
             obj = object_for(i, rank, world, n_obj)
-            last["losses"] = core.train_step(H, W, focal, poses[v], gts[v], obj)[0]
+            losses, rgb = core.train_step(H, W, focal, poses[v], gts[v], obj)
+            last["losses"] = losses
+            last["out"] = ({"loss_coarse": losses[0], "loss_fine": losses[1]} if args.n_fine
+                           else {"losses": losses})
+            last["out"]["rgb"] = rgb
+
+        def state():
+            return {"model_params": torch.cat([p.detach().reshape(-1) for p in model.param_list()]),
+                    "shape_codes": shape_codes, "texture_codes": texture_codes}
     views_per_step = n_views if args.config == "c4" else 1
     samples_per_step = R * (args.n_coarse + args.n_fine) * views_per_step
-    return dict(step=step, last=last, core=core, R=R, H=H, radius=radius, samples_per_step=samples_per_step)
+    return dict(step=step, last=last, state=state, core=core, R=R, H=H, radius=radius,
+                samples_per_step=samples_per_step)
 
 
 def weights_path(args):
@@ -325,9 +362,11 @@ def weights_path(args):
     return p
 
 
-def timed_run(wl, steps, warmup, timers, dist, dev):
+def timed_run(wl, steps, warmup, timers, dist, dev, per_kernel=True):
     """warmup untimed steps, then exactly `steps` steps between barriers +
-    synchronize; per-step HIP events (current stream) give the median."""
+    synchronize; per-step HIP events (current stream) give the median.
+    per_kernel: the hot launches of the timed steps record their own events
+    (Timers.mark) for the rooflines."""
     for i in range(warmup):
         wl["step"](i)
     torch.cuda.synchronize()
@@ -335,7 +374,7 @@ def timed_run(wl, steps, warmup, timers, dist, dev):
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
-    timers.on = True
+    timers.on = bool(per_kernel)
     # per-step marks: fence-less events (Timers.record), not torch events,
     # whose system-scope release would add an L2 write-back to every step
     marks = [timers._event() for _ in range(steps + 1)]
@@ -357,6 +396,31 @@ def timed_run(wl, steps, warmup, timers, dist, dev):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt, median = float(t[0]), float(t[1])
     return dt, median
+
+
+DUMP_BYTES = 60_000_000        # --dump-outputs: array bytes in all (files, headers included, stay below 64 MB)
+
+
+def dump_outputs(path, arrays, budget=DUMP_BYTES):
+    """Write name -> tensor as path/<name>.npy (float32; float64 stays
+    float64), at most ``budget`` bytes of array data in all: every array gets
+    an equal share, and one beyond its share is written as a fixed sample of
+    its flattened elements (sorted indices drawn with seed 0, so two runs
+    sample the same elements).  -> name -> [shape written, dtype, sampled]."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    written = {}
+    for name, t in arrays.items():
+        a = t.detach().to("cpu")
+        a = a.numpy() if a.dtype == torch.float64 else a.float().numpy()
+        sampled = a.nbytes > share
+        if sampled:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = [list(a.shape), str(a.dtype), sampled]
+    return written
 
 
 def main():
@@ -387,20 +451,27 @@ def main():
     timers = Timers()
     log(f"config {args.config}, precision {args.precision}, world {world}")
     wl = build_workload(args, dev, rank, world, args.precision, timers, dist)
-    clock = {"before_warmup": clock_probe(dev)}
-    dt, median = timed_run(wl, args.steps, args.warmup, timers, dist, dev)
-    clock["after_timed"] = clock_probe(dev)
+    clock = {}
+    if args.full:
+        clock["before_warmup"] = clock_probe(dev)
+    dt, median = timed_run(wl, args.steps, args.warmup, timers, dist, dev, per_kernel=args.full)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {**wl["last"]["out"], **wl["state"]()})
+        log(f"outputs of the last timed step in {args.dump_outputs}: {', '.join(dumped)}")
+    if args.full:
+        clock["after_timed"] = clock_probe(dev)
     samples_per_step = wl["samples_per_step"]
     value = samples_per_step * world * args.steps / dt
     ms = dt / args.steps * 1e3
 
-    roof = roofline(args, timers, samples_per_step, ms, wl["core"].step_impl.overlap_dw)
+    roof = roofline(args, timers, samples_per_step, ms, wl["core"].step_impl.overlap_dw) if args.full else None
     H, R, radius = wl["H"], wl["R"], wl["radius"]
 
     # the other precisions on the same C2 geometry (secondary figures): fp32
     # is the reference's arithmetic, bf16x3 its error-compensated stand-in
     others = {}
-    if args.config in ("c2", "c3") and not args.no_fp32:
+    if args.full and args.config in ("c2", "c3") and not args.no_fp32:
         del wl
         for prec in [p for p in PRECISIONS if p != args.precision]:
             t2 = Timers()
@@ -419,7 +490,7 @@ def main():
         clock["after_secondary"] = clock_probe(dev)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_threads, args)
 
     if rank == 0:
@@ -444,10 +515,12 @@ def main():
                        "name": args.config, "precision": args.precision,
                        "precision_note": PRECISION_NOTE[args.precision], "objects_per_step": world,
                        "rays_per_step_per_gpu": R, "parallelism": f"dp{world}"},
+            "full": args.full,
             "roofline": roof,
-            "clock": dict(clock, note=CLOCK_NOTE),
+            "clock": dict(clock, note=CLOCK_NOTE) if clock else None,
             "precisions": others or None,
             "cpu_baseline": cpu,
+            "dumped_outputs": dumped,
         }
         print(json.dumps(out))
     if dist is not None:
