@@ -122,13 +122,8 @@ int cn_plan_create(int shape_blocks, int texture_blocks, int W, int num_xyz_freq
   if (precision != CN_FP32 && precision != CN_BF16 && precision != CN_BF16X3 && precision != CN_BF16X3F)
     return fail("cn_plan_create: precision must be CN_FP32, CN_BF16, CN_BF16X3 or CN_BF16X3F");
   ChainSet cs;
-  if (shape_blocks == 3 && texture_blocks == 1)
-    cs = precision == CN_BF16X3F ? chain_set_bf16x3f_3_1() : precision == CN_BF16X3 ? chain_set_bf16x3_3_1()
-       : precision ? chain_set_bf16_3_1() : chain_set_fp32_3_1();
-  else if (shape_blocks == 2 && texture_blocks == 1)
-    cs = precision == CN_BF16X3F ? chain_set_bf16x3f_2_1() : precision == CN_BF16X3 ? chain_set_bf16x3_2_1()
-       : precision ? chain_set_bf16_2_1() : chain_set_fp32_2_1();
-  else return fail("cn_plan_create: unsupported (shape_blocks, texture_blocks); built: (3,1), (2,1)");
+  if (!find_chain_set(shape_blocks, texture_blocks, precision, &cs))
+    return fail("cn_plan_create: unsupported (shape_blocks, texture_blocks); built: (3,1), (2,1)");
   cn_plan* p = new cn_plan();
   p->cs = cs;
   p->h_fwd_idx = cs.fwd_table();
@@ -166,6 +161,43 @@ static int check_samples(long long M, const char* who) {
     return fail(std::string(who) + ": " + std::to_string(M) + " samples exceed CN_MAX_SAMPLES (" +
                 std::to_string((long long)CN_MAX_SAMPLES) + ") per call; split the rays into parts");
   return 0;
+}
+
+// Rows [act_row0, act_row0 + pad(M)) of an activation workspace laid out for
+// act_M samples (<= 0: M): the range check of every entry point that takes a
+// workspace.  act_row0 must be a multiple of align; the two messages follow
+// the entry point's name in cn_last_error.
+static int check_rows(const cn_plan* p, const char* who, int M, int* act_M, int act_row0, int align,
+                      const char* align_msg, const char* range_msg) {
+  if (check_samples(M, who)) return -1;
+  if (*act_M <= 0) *act_M = M;
+  if (check_samples(*act_M, (std::string(who) + " (act_M)").c_str())) return -1;
+  if (act_row0 < 0 || act_row0 % align) return fail(std::string(who) + align_msg);
+  if (act_row0 + cn_pad_samples(p, M) > cn_pad_samples(p, *act_M)) return fail(std::string(who) + range_msg);
+  return 0;
+}
+constexpr const char* kTileMsg = ": act_row0 must be a multiple of the tile";
+constexpr const char* kRangeMsg = ": rows exceed the activation workspace";
+
+// Points a chain launch at rows [act_row0, ...) of the workspace (coarse and
+// fine passes share one workspace, so one backward / dW covers both).  The lo
+// planes exist in the bf16x3 layout only, and only the forward reads them.
+static void bind_workspace(ChainArgs& a, const cn_plan* p, void* d_act, int act_M, int act_row0) {
+  const ActLayout L = p->cs.layout(cn_pad_samples(p, act_M));
+  const size_t es = p->cs.prec ? 2 : 4;
+  const size_t r0 = (size_t)act_row0;
+  char* b = (char*)d_act;
+  a.pe = b + L.pe + r0 * 64 * es;
+  a.dir = b + L.dir + r0 * 32 * es;
+  for (int i = 0; i < kMaxPlanes; ++i) {
+    a.Y[i] = b + L.Y[i] + r0 * L.Yw[i] * es;
+    a.dA[i] = b + L.dA[i] + r0 * L.dAw[i] * es;
+  }
+  a.d8 = b + L.d8 + r0 * 32 * es;
+  a.spre = (float*)(b + L.spre) + r0;
+  a.masks = (uint32_t*)(b + L.masks + (r0 / 32) * L.mask_bytes_per_slab);
+  a.pelo = L.pelo ? b + L.pelo + r0 * 64 * es : nullptr;
+  for (int i = 0; i < kMaxPlanes; ++i) a.Ylo[i] = L.Ylo[i] ? b + L.Ylo[i] + r0 * L.Yw[i] * es : nullptr;
 }
 
 void cn_plan_destroy(cn_plan* p) {
@@ -273,28 +305,9 @@ static int mlp_fwd_impl(int codes, const cn_plan* p, const void* d_pack, const f
   const int Mp = cn_pad_samples(p, M);
   if (d_act) {
     // the workspace may be sized for act_M samples, this launch filling rows
-    // [act_row0, act_row0 + Mp) of it (coarse and fine passes share one
-    // workspace, so one backward / dW covers both)
-    if (act_M <= 0) act_M = M;
-    if (check_samples(act_M, "cn_mlp_fwd (act_M)")) return -1;
-    if (act_row0 < 0 || act_row0 % p->cs.tile) return fail("cn_mlp_fwd: act_row0 must be a multiple of the tile");
-    const int Ma = cn_pad_samples(p, act_M);
-    if (act_row0 + Mp > Ma) return fail("cn_mlp_fwd: rows exceed the activation workspace");
-    const ActLayout L = p->cs.layout(Ma);
-    const size_t es = p->cs.prec ? 2 : 4;
-    const size_t r0 = (size_t)act_row0;
-    char* b = (char*)d_act;
-    a.pe = b + L.pe + r0 * 64 * es;
-    a.dir = b + L.dir + r0 * 32 * es;
-    for (int i = 0; i < kMaxPlanes; ++i) {
-      a.Y[i] = b + L.Y[i] + r0 * L.Yw[i] * es;
-      a.dA[i] = b + L.dA[i] + r0 * L.dAw[i] * es;
-    }
-    a.d8 = b + L.d8 + r0 * 32 * es;
-    a.spre = (float*)(b + L.spre) + r0;
-    a.masks = (uint32_t*)(b + L.masks + (r0 / 32) * L.mask_bytes_per_slab);
-    a.pelo = L.pelo ? b + L.pelo + r0 * 64 * es : nullptr;
-    for (int i = 0; i < kMaxPlanes; ++i) a.Ylo[i] = L.Ylo[i] ? b + L.Ylo[i] + r0 * L.Yw[i] * es : nullptr;
+    // [act_row0, act_row0 + Mp) of it
+    if (check_rows(p, "cn_mlp_fwd", M, &act_M, act_row0, p->cs.tile, kTileMsg, kRangeMsg)) return -1;
+    bind_workspace(a, p, d_act, act_M, act_row0);
   }
   const int grid = (Mp + p->cs.waves_fwd * 32 - 1) / (p->cs.waves_fwd * 32);
   launch_hot(d_act ? (codes ? p->cs.fwd_codes : p->cs.fwd_train) : p->cs.fwd_infer, dim3(grid),
@@ -323,7 +336,7 @@ static int mlp_bwd_impl(int codes, const cn_plan* p, const void* d_pack, const f
                         void* stream) {
   HotCallScope hot;
   if (!p || !d_pack || !d_blob || !d_dsigma || !d_drgb || !d_act) return fail("cn_mlp_bwd: NULL argument");
-  if (check_samples(M, "cn_mlp_bwd")) return -1;
+  if (check_rows(p, "cn_mlp_bwd", M, &act_M, act_row0, p->cs.tile, kTileMsg, kRangeMsg)) return -1;
   ChainArgs a{};
   a.wpack = d_pack;
   a.bias = d_blob;
@@ -331,25 +344,7 @@ static int mlp_bwd_impl(int codes, const cn_plan* p, const void* d_pack, const f
   a.dsigma = d_dsigma;
   a.drgb = d_drgb;
   const int Mp = cn_pad_samples(p, M);
-  // rows [act_row0, act_row0 + Mp) of a workspace laid out for act_M samples
-  if (act_M <= 0) act_M = M;
-  if (check_samples(act_M, "cn_mlp_bwd (act_M)")) return -1;
-  if (act_row0 < 0 || act_row0 % p->cs.tile) return fail("cn_mlp_bwd: act_row0 must be a multiple of the tile");
-  const int Ma = cn_pad_samples(p, act_M);
-  if (act_row0 + Mp > Ma) return fail("cn_mlp_bwd: rows exceed the activation workspace");
-  const ActLayout L = p->cs.layout(Ma);
-  const size_t es = p->cs.prec ? 2 : 4;
-  const size_t r0 = (size_t)act_row0;
-  char* b = (char*)d_act;
-  a.pe = b + L.pe + r0 * 64 * es;
-  a.dir = b + L.dir + r0 * 32 * es;
-  for (int i = 0; i < kMaxPlanes; ++i) {
-    a.Y[i] = b + L.Y[i] + r0 * L.Yw[i] * es;
-    a.dA[i] = b + L.dA[i] + r0 * L.dAw[i] * es;
-  }
-  a.d8 = b + L.d8 + r0 * 32 * es;
-  a.spre = (float*)(b + L.spre) + r0;
-  a.masks = (uint32_t*)(b + L.masks + (r0 / 32) * L.mask_bytes_per_slab);
+  bind_workspace(a, p, d_act, act_M, act_row0);
   launch_hot(codes ? p->cs.bwd_codes : p->cs.bwd, dim3((Mp + p->cs.waves_bwd * 32 - 1) / (p->cs.waves_bwd * 32)),
              dim3(p->cs.waves_bwd * 64), S(stream), a);
   return launch_check("chain_kernel(bwd)");
@@ -375,11 +370,8 @@ static int mlp_dw_impl(const cn_plan* p, void* d_act, int act_M, int act_row0, i
                        void* d_ws, void* stream) {
   HotCallScope hot;
   if (!p || !d_act || !d_zvec || !d_params || !d_grads || !d_dbuf || !d_ws) return fail("cn_mlp_dw: NULL argument");
-  if (check_samples(M, "cn_mlp_dw")) return -1;
-  if (act_M <= 0) act_M = M;
-  if (check_samples(act_M, "cn_mlp_dw (act_M)")) return -1;
-  if (act_row0 < 0 || act_row0 % 256 || act_row0 + cn_pad_samples(p, M) > cn_pad_samples(p, act_M))
-    return fail("cn_mlp_dw: rows exceed the activation workspace (act_row0 must be a multiple of 256)");
+  constexpr const char* msg = ": rows exceed the activation workspace (act_row0 must be a multiple of 256)";
+  if (check_rows(p, "cn_mlp_dw", M, &act_M, act_row0, 256, msg, msg)) return -1;
   DwArgs dw;
   DwRedArgs red;
   if (nwg_req < 0 || nwg_req > 256) return fail("cn_mlp_dw_rows: n_workgroups must be in [0, 256]");
@@ -415,12 +407,11 @@ int cn_mlp_dw_rows(const cn_plan* p, void* d_act, int act_M, int act_row0, int M
 int cn_mlp_dbias(const cn_plan* p, void* d_act, int act_M, int M, float* d_dbuf, void* d_ws, void* stream) {
   HotCallScope hot;
   if (!p || !d_act || !d_dbuf || !d_ws) return fail("cn_mlp_dbias: NULL argument");
-  if (check_samples(M, "cn_mlp_dbias")) return -1;
-  if (act_M <= 0) act_M = M;
-  if (check_samples(act_M, "cn_mlp_dbias (act_M)")) return -1;
+  constexpr const char* msg = ": rows exceed the workspace or unsupported plane width";
+  if (check_rows(p, "cn_mlp_dbias", M, &act_M, 0, 1, msg, msg)) return -1;
   DbArgs db;
   if (p->cs.db_setup((char*)d_act, act_M, M, d_dbuf, (char*)d_ws, &db) < 0)
-    return fail("cn_mlp_dbias: rows exceed the workspace or unsupported plane width");
+    return fail(std::string("cn_mlp_dbias") + msg);
   if (db.ninj <= 0) return 0;
   if (p->cs.prec) launch_hot(db_kernel<CN_P_BF16>, dim3(kDbBlocks, db.ninj), dim3(256), S(stream), db);
   else launch_hot(db_kernel<CN_P_FP32>, dim3(kDbBlocks, db.ninj), dim3(256), S(stream), db);

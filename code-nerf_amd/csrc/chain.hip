@@ -1049,10 +1049,12 @@ struct Chain {
 // 4-wave workgroups -> 2 (two workgroups per CU, so one's prologue and
 // epilogues run beside the other's MFMAs); fp32 and bf16x3 4-wave -> 1
 // (512 VGPRs)
+#define CN_CHAIN_BOUNDS __launch_bounds__(WAVES * 64, (WAVES >= 8 ? WAVES / 4 : (P == CN_P_BF16 ? 2 : 1)))
+// Declared only: chain_kernel_inst.hip defines it and instantiates one kernel
+// per object (Makefile KERNELS), so a unit that takes a chain kernel's address
+// (plans.hip) emits a reference, never the kernel.  The definition repeats the
+// bounds (the compiler crashes on bounds it has to inherit from here).
 template <int P, int SB, int TB, bool BWD, int WAVES, int MODE>
-__global__ __launch_bounds__(WAVES * 64, (WAVES >= 8 ? WAVES / 4 : (P == CN_P_BF16 ? 2 : 1))) void
-chain_kernel(ChainArgs a) {
-  Chain<P, SB, TB, BWD, WAVES, MODE>::run(a);
-}
+__global__ CN_CHAIN_BOUNDS void chain_kernel(ChainArgs a);
 
 }  // namespace cn

@@ -1,4 +1,4 @@
-// Per-configuration kernel sets (one translation unit per precision x net).
+// A plan's kernel set: what capi.hip sees of a (net, precision) plan.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -27,7 +27,6 @@ struct ActLayout {
 
 struct ChainSet {
   int prec = 0, SB = 0, TB = 0;      // prec: plane / dW element type (0 fp32, 1 bf16)
-  int x3 = 0;                         // chain kernels in bf16x3 (CN_P_BF16X3)
   int waves_fwd = 0, waves_bwd = 0;   // waves per workgroup of the forward / backward chain kernels
   int tile = 0;                        // row alignment of a launch (the 256-sample pad granule)
   int n_params = 0, n_inject = 0, n_fwd_layers = 0;
@@ -54,13 +53,7 @@ struct ChainSet {
   int (*db_setup)(char* act, int act_M, int M, float* dbuf, char* ws, DbArgs* db) = nullptr;
 };
 
-ChainSet chain_set_fp32_3_1();
-ChainSet chain_set_bf16_3_1();
-ChainSet chain_set_fp32_2_1();
-ChainSet chain_set_bf16_2_1();
-ChainSet chain_set_bf16x3_3_1();
-ChainSet chain_set_bf16x3_2_1();
-ChainSet chain_set_bf16x3f_3_1();
-ChainSet chain_set_bf16x3f_2_1();
+// Looks the plan up in the plan table (plans.hip); false: no such plan is built.
+bool find_chain_set(int shape_blocks, int texture_blocks, int precision, ChainSet* out);
 
 }  // namespace cn

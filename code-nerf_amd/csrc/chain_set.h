@@ -1,10 +1,9 @@
 // Host-side construction of a ChainSet: packing tables (weight element ->
 // reference tensor element), activation-workspace layout, dW problem setup.
-// Included by the per-configuration translation units.
+// Included by the plan unit (plans.hip).
 #pragma once
 #include <algorithm>
 #include "chain.hip"
-#include "chain_extern.h"
 #include "chain_inst.h"
 #include "dw_args.h"
 #include "latent.hip"
@@ -316,19 +315,27 @@ int db_setup(char* act, int act_M, int M, float* dbuf, char* ws, DbArgs* db) {
   return n;
 }
 
-template <int P, int SB, int TB>
+// One plan = (PF, PB): the arithmetic of the forward chains and that of the
+// backward -- dX chain, stored planes, dW pass (cn_common.h).  CN_BF16X3F is
+// (bf16x3, bf16): its training forward stores the hi planes only
+// (CN_MODE_TRAIN_HI -- exactly the bf16 plan's planes: the same layout, masks
+// and rounding rn(x)), which the bf16 dX chain and the bf16 dW pass read.
+// bf16: 8-wave workgroups (two waves per SIMD, one workgroup per CU); fp32
+// (bin operand of 144 VGPRs) and bf16x3 (hi + lo operands, 2 x 72 VGPRs,
+// beside 128 accumulator registers): 4 waves, one per SIMD (round 5 measured
+// a 16-sample, two-waves-per-SIMD bf16x3 layout and kept this one: DESIGN.md
+// section 7, Round 5)
+constexpr int chain_waves(int P) { return P == CN_P_BF16 ? 8 : 4; }
+
+// Every chain kernel named here needs its word in the Makefile's KERNELS
+// (P_SB_TB_BWD_WAVES_MODE); a missing one is an undefined symbol at the link.
+template <int PF, int PB, int SB, int TB>
 ChainSet make_chain_set() {
   using N = Net<SB, TB>;
-  // bf16: 8-wave workgroups (two waves per SIMD, one workgroup per CU) by
-  // default; fp32 (bin operand of 144 VGPRs) and bf16x3 (hi + lo operands,
-  // 2 x 72 VGPRs, beside 128 accumulator registers): 4 waves, one per SIMD
-  // (round 5 measured a 16-sample, two-waves-per-SIMD bf16x3 layout and kept
-  // this one: DESIGN.md section 7, Round 5)
-  constexpr int WF = P == CN_P_BF16 ? 8 : 4;
-  constexpr int WB = P == CN_P_BF16 ? 8 : 4;
+  constexpr int WF = chain_waves(PF), WB = chain_waves(PB);
+  constexpr int TRAIN = PF == CN_P_BF16X3 && PB == CN_P_BF16 ? CN_MODE_TRAIN_HI : CN_MODE_TRAIN;
   ChainSet s;
-  s.prec = P != CN_P_FP32;     // activation-plane element type: 1 = bf16 (bf16, bf16x3)
-  s.x3 = P == CN_P_BF16X3;
+  s.prec = PB != CN_P_FP32;     // activation-plane element type: 1 = bf16 (bf16, bf16x3)
   s.SB = SB;
   s.TB = TB;
   s.waves_fwd = WF;
@@ -338,65 +345,23 @@ ChainSet make_chain_set() {
   s.n_inject = N::kInject;
   s.n_fwd_layers = N::kFwdLayers;
   s.blob_floats = BiasBlob<SB, TB>::kFloats;
-  s.pack_fwd_bytes = Sched<P, SB, TB, false>::packed_bytes();
-  s.pack_bwd_bytes = Sched<P, SB, TB, true>::packed_bytes();
-  s.fwd_train = chain_kernel<P, SB, TB, false, WF, CN_MODE_TRAIN>;
-  s.fwd_infer = chain_kernel<P, SB, TB, false, WF, CN_MODE_INFER>;
-  s.fwd_codes = chain_kernel<P, SB, TB, false, WF, CN_MODE_CODES>;
-  s.bwd = chain_kernel<P, SB, TB, true, WB, CN_MODE_TRAIN>;
-  s.bwd_codes = chain_kernel<P, SB, TB, true, WB, CN_MODE_CODES>;
-  s.fwd_table = build_pack_table<P, SB, TB, false>;
-  s.bwd_table = build_pack_table<P, SB, TB, true>;
+  s.pack_fwd_bytes = Sched<PF, SB, TB, false>::packed_bytes();
+  s.pack_bwd_bytes = Sched<PB, SB, TB, true>::packed_bytes();
+  s.fwd_train = chain_kernel<PF, SB, TB, false, WF, TRAIN>;
+  s.fwd_infer = chain_kernel<PF, SB, TB, false, WF, CN_MODE_INFER>;
+  s.fwd_codes = chain_kernel<PF, SB, TB, false, WF, CN_MODE_CODES>;
+  s.bwd = chain_kernel<PB, SB, TB, true, WB, CN_MODE_TRAIN>;
+  s.bwd_codes = chain_kernel<PB, SB, TB, true, WB, CN_MODE_CODES>;
+  s.fwd_table = build_pack_table<PF, SB, TB, false>;
+  s.bwd_table = build_pack_table<PB, SB, TB, true>;
   s.latent_fwd = latent_fwd_kernel<SB, TB>;
   s.latent_bwd = latent_bwd_kernel<SB, TB>;
   s.code_grad = code_grad_kernel<SB, TB>;
-  s.layout = act_layout<P, SB, TB>;
-  s.dw_setup = dw_setup<P, SB, TB>;
-  s.dw_ws_bytes = dw_ws_bytes<P, SB, TB>;
+  s.layout = act_layout<PB, SB, TB>;
+  s.dw_setup = dw_setup<PB, SB, TB>;
+  s.dw_ws_bytes = dw_ws_bytes<PB, SB, TB>;
   s.fold_args = fold_args<SB, TB>;
-  s.db_setup = db_setup<P, SB, TB>;
-  return s;
-}
-
-// CN_P_BF16X3F: the bf16x3 forward chains (rgb within ~5e-7 of the fp32
-// reference) with the CN_P_BF16 backward: the training forward stores the hi
-// planes only (CN_MODE_TRAIN_HI -- exactly the bf16 plan's planes: the same
-// layout, masks and rounding rn(x)), which the bf16 dX chain (8 waves) and the
-// bf16 dW pass read.  Weight packs: forward = bf16x3 (W_hi, W_lo fragments),
-// backward = bf16.
-template <int SB, int TB>
-ChainSet make_chain_set_x3f() {
-  using N = Net<SB, TB>;
-  constexpr int X3 = CN_P_BF16X3, B16 = CN_P_BF16;
-  ChainSet s;
-  s.prec = 1;                 // bf16 planes and dW
-  s.x3 = 1;                   // forward chains in bf16x3
-  s.SB = SB;
-  s.TB = TB;
-  s.waves_fwd = 4;            // as the bf16x3 plan
-  s.waves_bwd = 8;            // as the bf16 plan
-  s.tile = 256;
-  s.n_params = ParamIdx{SB, TB}.count();
-  s.n_inject = N::kInject;
-  s.n_fwd_layers = N::kFwdLayers;
-  s.blob_floats = BiasBlob<SB, TB>::kFloats;
-  s.pack_fwd_bytes = Sched<X3, SB, TB, false>::packed_bytes();
-  s.pack_bwd_bytes = Sched<B16, SB, TB, true>::packed_bytes();
-  s.fwd_train = chain_kernel<X3, SB, TB, false, 4, CN_MODE_TRAIN_HI>;
-  s.fwd_infer = chain_kernel<X3, SB, TB, false, 4, CN_MODE_INFER>;
-  s.fwd_codes = chain_kernel<X3, SB, TB, false, 4, CN_MODE_CODES>;
-  s.bwd = chain_kernel<B16, SB, TB, true, 8, CN_MODE_TRAIN>;
-  s.bwd_codes = chain_kernel<B16, SB, TB, true, 8, CN_MODE_CODES>;
-  s.fwd_table = build_pack_table<X3, SB, TB, false>;
-  s.bwd_table = build_pack_table<B16, SB, TB, true>;
-  s.latent_fwd = latent_fwd_kernel<SB, TB>;
-  s.latent_bwd = latent_bwd_kernel<SB, TB>;
-  s.code_grad = code_grad_kernel<SB, TB>;
-  s.layout = act_layout<B16, SB, TB>;
-  s.dw_setup = dw_setup<B16, SB, TB>;
-  s.dw_ws_bytes = dw_ws_bytes<B16, SB, TB>;
-  s.fold_args = fold_args<SB, TB>;
-  s.db_setup = db_setup<B16, SB, TB>;
+  s.db_setup = db_setup<PB, SB, TB>;
   return s;
 }
 

@@ -22,9 +22,12 @@ typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 // into one fp32 accumulator: A_hi B_hi + A_hi B_lo + A_lo B_hi (the lo x lo
 // term, ~2^-16 relative, is dropped).  Activation planes (the dW operands)
 // are stored as in CN_P_BF16.
-// CN_P_BF16X3F (a plan, not a kernel arithmetic): the bf16x3 forward chain
-// (rendered rgb at fp32 class) feeding the CN_P_BF16 backward -- dX chain and
-// dW pass on bf16 operands; the forward stores the hi planes only
+// A plan pairs the arithmetic of its forward chains with that of its backward
+// (dX chain, stored planes, dW pass): the rows of the plan table in plans.hip,
+// built by make_chain_set<PF, PB, ...> (chain_set.h).  fp32, bf16 and bf16x3
+// use one arithmetic for both.  CN_P_BF16X3F is a plan only, not a kernel
+// arithmetic: the bf16x3 forward chain (rendered rgb at fp32 class) feeding
+// the CN_P_BF16 backward; the forward stores the hi planes only
 // (CN_MODE_TRAIN_HI), which are the CN_P_BF16 planes' format.
 enum { CN_P_FP32 = 0, CN_P_BF16 = 1, CN_P_BF16X3 = 2, CN_P_BF16X3F = 3 };
 

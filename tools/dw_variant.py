@@ -31,11 +31,12 @@ def main():
     open(p, "w").write(s)
     obj = os.path.join(tmp, "capi.o")
     subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, "-c", os.path.join(src, "capi.hip"), "-o", obj], check=True)
+    # the plan unit and every chain kernel object (csrc/Makefile: plans.o, k_*.o)
     insts = sorted(os.path.join(CSRC, "build", f) for f in os.listdir(os.path.join(CSRC, "build"))
-                   if f.startswith("inst_") and f.endswith(".o"))
+                   if f.endswith(".o") and f != "capi.o")
     out = os.path.join(REPO, "code-nerf_amd", f"libcodenerf_hip_{name}.so")
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out, obj, *insts],
-                   check=True)
+    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-z,defs", "-o", out, obj,
+                    *insts], check=True)
     print("built", out)
 
 
