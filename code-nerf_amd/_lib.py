@@ -18,7 +18,7 @@ _IN_TREE = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 # product path (tests, smoke, bench) always runs the in-tree library.
 LIB_PATH = os.environ.get("CODENERF_LIB") or _IN_TREE
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 CN_FP32 = 0
 CN_BF16 = 1
 CN_BF16X3 = 2
@@ -62,6 +62,10 @@ _SIGS = {
     "cn_mlp_bwd": (_I, [_P, _P, _P, _I, _P, _P, _P, _P]),
     "cn_mlp_fwd_codes": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _P]),
     "cn_mlp_bwd_codes": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _P]),
+    "cn_mlp_bwd_pose": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _P]),
+    "cn_mlp_input_grad": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "cn_get_rays_bwd_ws_bytes": (_Z, [_I, _I]),
+    "cn_get_rays_bwd": (_I, [_I, _I, _D, _I, _P, _P, _P, _P, _P, _P]),
     "cn_mlp_dw": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "cn_mlp_bwd_rows": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _P]),
     "cn_mlp_dw_rows": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P]),

@@ -14,6 +14,7 @@
 #include "dw.hip"
 #include "optim.hip"
 #include "render.hip"
+#include "inputgrad.hip"
 #include "probe.hip"
 
 using namespace cn;
@@ -345,7 +346,9 @@ static int mlp_bwd_impl(int codes, const cn_plan* p, const void* d_pack, const f
   a.drgb = d_drgb;
   const int Mp = cn_pad_samples(p, M);
   bind_workspace(a, p, d_act, act_M, act_row0);
-  launch_hot(codes ? p->cs.bwd_codes : p->cs.bwd, dim3((Mp + p->cs.waves_bwd * 32 - 1) / (p->cs.waves_bwd * 32)),
+  // codes: 0 the training backward, 1 CN_MODE_CODES, 2 CN_MODE_POSE
+  launch_hot(codes == 2 ? p->cs.bwd_pose : codes ? p->cs.bwd_codes : p->cs.bwd,
+             dim3((Mp + p->cs.waves_bwd * 32 - 1) / (p->cs.waves_bwd * 32)),
              dim3(p->cs.waves_bwd * 64), S(stream), a);
   return launch_check("chain_kernel(bwd)");
 }
@@ -363,6 +366,64 @@ int cn_mlp_bwd_rows(const cn_plan* p, const void* d_pack, const float* d_blob, i
 int cn_mlp_bwd_codes(const cn_plan* p, const void* d_pack, const float* d_blob, int M, const float* d_dsigma,
                      const float* d_drgb, void* d_act, int act_M, int act_row0, void* stream) {
   return mlp_bwd_impl(1, p, d_pack, d_blob, M, d_dsigma, d_drgb, d_act, act_M, act_row0, stream);
+}
+
+int cn_mlp_bwd_pose(const cn_plan* p, const void* d_pack, const float* d_blob, int M, const float* d_dsigma,
+                    const float* d_drgb, void* d_act, int act_M, int act_row0, void* stream) {
+  return mlp_bwd_impl(2, p, d_pack, d_blob, M, d_dsigma, d_drgb, d_act, act_M, act_row0, stream);
+}
+
+int cn_mlp_input_grad(const cn_plan* p, const float* const* d_params, const void* d_act, int act_M, int act_row0,
+                      int M, const float* d_xyz, const float* d_viewdir, const float* d_rays_o,
+                      const float* d_rays_d, const float* d_z, int z_stride, int n_samples, float* d_dxyz,
+                      float* d_dviewdir, float* d_drays_o, float* d_drays_d, void* stream) {
+  if (!p || !d_params || !d_act || !d_dxyz || !d_dviewdir) return fail("cn_mlp_input_grad: NULL argument");
+  if (check_rows(p, "cn_mlp_input_grad", M, &act_M, act_row0, p->cs.tile, kTileMsg, kRangeMsg)) return -1;
+  if ((d_drays_o == nullptr) != (d_drays_d == nullptr))
+    return fail("cn_mlp_input_grad: give both per-ray outputs or none");
+  InputGradArgs a{};
+  a.params = d_params;
+  a.w_vd = ParamIdx{p->cs.SB, p->cs.TB}.viewdir_w();
+  a.M = M;
+  a.Mp = cn_pad_samples(p, M);
+  if (d_xyz) {
+    if (!d_viewdir) return fail("cn_mlp_input_grad: xyz given without viewdir");
+    if (d_drays_o) return fail("cn_mlp_input_grad: per-ray outputs need ray mode");
+    a.mode = 0;
+    a.xyz = d_xyz;
+    a.vdir = d_viewdir;
+    a.nsamp = 1;
+  } else {
+    if (!d_rays_o || !d_rays_d || !d_z || n_samples <= 0)
+      return fail("cn_mlp_input_grad: ray mode needs rays_o, rays_d, z, n_samples");
+    if (M % n_samples) return fail("cn_mlp_input_grad: M must be a multiple of n_samples in ray mode");
+    if (z_stride != 0 && z_stride != n_samples) return fail("cn_mlp_input_grad: z_stride must be 0 or n_samples");
+    a.mode = 1;
+    a.rays_o = d_rays_o;
+    a.rays_d = d_rays_d;
+    a.zvals = d_z;
+    a.z_stride = z_stride;
+    a.nsamp = n_samples;
+  }
+  const ActLayout L = p->cs.layout(cn_pad_samples(p, act_M));
+  const size_t es = p->cs.prec ? 2 : 4;
+  const int vd = p->cs.SB + 2;           // plane of encoding_viewdir
+  if (L.dAw[0] != 256 || L.dAw[vd] != 288) return fail("cn_mlp_input_grad: unexpected plane widths");
+  a.dA0 = (const char*)d_act + L.dA[0] + (size_t)act_row0 * L.dAw[0] * es;
+  a.dAv = (const char*)d_act + L.dA[vd] + (size_t)act_row0 * L.dAw[vd] * es;
+  a.dxyz = d_dxyz;
+  a.dvdir = d_dviewdir;
+  const int grid = std::min(kIgMaxWorkgroups, grid_for(a.Mp / 32, kIgWaves));
+  if (p->cs.prec) hipLaunchKernelGGL(input_grad_kernel<true>, dim3(grid), dim3(kIgWaves * 64), 0, S(stream), a);
+  else hipLaunchKernelGGL(input_grad_kernel<false>, dim3(grid), dim3(kIgWaves * 64), 0, S(stream), a);
+  if (launch_check("input_grad_kernel")) return -1;
+  if (d_drays_o) {
+    const int R = M / n_samples;
+    hipLaunchKernelGGL(ray_grad_kernel, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), d_dxyz, d_dviewdir, d_z,
+                       z_stride, R, n_samples, d_drays_o, d_drays_d);
+    return launch_check("ray_grad_kernel");
+  }
+  return 0;
 }
 
 static int mlp_dw_impl(const cn_plan* p, void* d_act, int act_M, int act_row0, int M, const float* d_zvec,
@@ -439,6 +500,24 @@ int cn_get_rays(int H, int W, double focal, int focal_is_f64, const float* d_c2w
   hipLaunchKernelGGL(get_rays_kernel, dim3(grid_for((long)H * W, 256)), dim3(256), 0, S(stream), H, W, focal,
                      focal_is_f64, d_c2w, d_ro, d_vd);
   return launch_check("get_rays_kernel");
+}
+
+size_t cn_get_rays_bwd_ws_bytes(int H, int W) {
+  if (H <= 0 || W <= 0 || (long long)H * W > CN_MAX_SAMPLES) return 0;
+  return (size_t)grid_for((long)H * W, kRaysBwdBlock) * 12 * sizeof(double);
+}
+
+int cn_get_rays_bwd(int H, int W, double focal, int focal_is_f64, const float* d_c2w, const float* d_dro,
+                    const float* d_dvd, float* d_dc2w, void* d_ws, void* stream) {
+  if (!d_c2w || !d_dro || !d_dvd || !d_dc2w || !d_ws || H <= 0 || W <= 0) return fail("cn_get_rays_bwd: bad argument");
+  if (check_samples((long long)H * W, "cn_get_rays_bwd")) return -1;
+  const int nb = grid_for((long)H * W, kRaysBwdBlock);
+  hipLaunchKernelGGL(get_rays_bwd_partial_kernel, dim3(nb), dim3(kRaysBwdBlock), 0, S(stream), H, W, focal,
+                     focal_is_f64, d_c2w, d_dro, d_dvd, (double*)d_ws);
+  if (launch_check("get_rays_bwd_partial_kernel")) return -1;
+  hipLaunchKernelGGL(get_rays_bwd_final_kernel, dim3(1), dim3(kRaysBwdBlock), 0, S(stream), (const double*)d_ws, nb,
+                     d_dc2w);
+  return launch_check("get_rays_bwd_final_kernel");
 }
 
 int cn_sample_points(const float* d_ro, const float* d_vd, const float* d_z, int z_stride, int R, int N,

@@ -176,6 +176,7 @@ struct Chain {
   // hold), so the weight gradients multiply hi + lo (dw.hip DwBody<..., LO>)
   static constexpr bool kXlo = kX3 && MODE == CN_MODE_TRAIN && !BWD;
   static_assert(MODE != CN_MODE_TRAIN_HI || (kX3 && !BWD), "TRAIN_HI is the bf16x3 forward of a bf16x3f plan");
+  static_assert(MODE != CN_MODE_POSE || BWD, "POSE is a backward mode: a pose step runs the CODES forward");
   static constexpr int NL = S::NL;
   static constexpr int kChunks = S::kChunks;
   // waves that issue the weight stream's LDS-DMA (all of them when WAVES
@@ -268,7 +269,13 @@ struct Chain {
   // queue at the same time).  Store j of layer li-1 follows block
   // first_block(li) + j * lblocks(li) / n.  The last layer's plane (backward:
   // dA of the first forward layer) has no next layer and is stored in place.
-  static constexpr bool codes_plane(int p) { return MODE == CN_MODE_CODES && p >= 1 && N::fwd(p - 1).inj >= 0; }
+  // CN_MODE_POSE adds the input-side planes: plane 0 (encoding_xyz, the last
+  // backward layer's: stored in place) and plane SB + 2 (encoding_viewdir;
+  // its sigma-head column 256 is a PLANES prologue store and stays unwritten)
+  static constexpr bool codes_plane(int p) {
+    if (MODE == CN_MODE_POSE && (p == 0 || p == SB + 2)) return true;
+    return (MODE == CN_MODE_CODES || MODE == CN_MODE_POSE) && p >= 1 && N::fwd(p - 1).inj >= 0;
+  }
   static constexpr bool plane_of(int i) {
     const int p = S::L(i).plane;
     return BWD ? ((PLANES && N::stored(p)) || codes_plane(p)) : (PLANES && p >= 0 && N::stored(p));

@@ -16,6 +16,10 @@ enum ChainMode : int {
                        // planes of the layers fed by a code (the bias sums need them)
   CN_MODE_TRAIN_HI = 3,  // bf16x3 forward, training: every plane of CN_MODE_TRAIN but
                          // not the X lo planes (CN_P_BF16X3F: a bf16 dW reads hi only)
+  CN_MODE_POSE = 4,    // backward only, behind a CN_MODE_CODES forward: the planes of
+                       // CN_MODE_CODES plus the two input-side gradient planes the
+                       // input-gradient kernel reads (inputgrad.hip): dA of encoding_xyz
+                       // and the 256 feature columns of dA of encoding_viewdir
 };
 
 // Per-call bias blob (written by the latent kernel, read by the forward chain):

@@ -37,6 +37,7 @@ struct ChainSet {
   void (*bwd)(ChainArgs) = nullptr;
   void (*fwd_codes)(ChainArgs) = nullptr;   // codes-only optimisation (CN_MODE_CODES)
   void (*bwd_codes)(ChainArgs) = nullptr;
+  void (*bwd_pose)(ChainArgs) = nullptr;    // bwd_codes + the input-side dA planes (CN_MODE_POSE)
   void (*latent_fwd)(LatentArgs) = nullptr;
   void (*latent_bwd)(LatentBwdArgs) = nullptr;
   void (*code_grad)(LatentBwdArgs) = nullptr;

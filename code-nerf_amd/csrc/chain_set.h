@@ -352,6 +352,7 @@ ChainSet make_chain_set() {
   s.fwd_codes = chain_kernel<PF, SB, TB, false, WF, CN_MODE_CODES>;
   s.bwd = chain_kernel<PB, SB, TB, true, WB, CN_MODE_TRAIN>;
   s.bwd_codes = chain_kernel<PB, SB, TB, true, WB, CN_MODE_CODES>;
+  s.bwd_pose = chain_kernel<PB, SB, TB, true, WB, CN_MODE_POSE>;
   s.fwd_table = build_pack_table<PF, SB, TB, false>;
   s.bwd_table = build_pack_table<PB, SB, TB, true>;
   s.latent_fwd = latent_fwd_kernel<SB, TB>;

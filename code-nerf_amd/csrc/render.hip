@@ -49,6 +49,104 @@ __global__ __launch_bounds__(256) void get_rays_kernel(int H, int W, double foca
   }
 }
 
+// Autograd of get_rays with respect to c2w (no reference counterpart: the
+// reference never differentiates through the camera).  With cam = (dx, dy, -1),
+// d = R cam, v = d / |d|:
+//   g = (d_v - v (v . d_v)) / |d|,  dR[a][b] = sum_rays g_a cam_b,
+//   d c2w[a][3] = sum_rays d_rays_o_a.
+// d and |d| are the forward's float values; everything after them, and both
+// stages of the sum, in float64.  Stage 1: one partial (12 doubles, the 3 x 4
+// row-major layout of the output) per 256-pixel block, summed by a fixed
+// butterfly and a fixed order over the block's waves; stage 2: one block sums
+// the partials in a fixed order.  Written, not accumulated; deterministic.
+constexpr int kRaysBwdBlock = 256;
+
+CN_DEV double shfl_xor_d(double v, int k) {
+  return __hiloint2double(__shfl_xor(__double2hiint(v), k), __shfl_xor(__double2loint(v), k));
+}
+
+__global__ __launch_bounds__(kRaysBwdBlock) void get_rays_bwd_partial_kernel(
+    int H, int W, double focal, int focal_f64, const float* __restrict__ c2w, const float* __restrict__ dro,
+    const float* __restrict__ dvd, double* __restrict__ part) {
+  __shared__ double red[kRaysBwdBlock / 64][12];
+  const int p = blockIdx.x * kRaysBwdBlock + threadIdx.x;
+  double t[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) t[i] = 0.0;
+  if (p < H * W) {
+    const int row = p / W, col = p - row * W;
+    float cam[3];
+    if (focal_f64) {
+      cam[0] = (float)(((double)col - W * 0.5) / focal);
+      cam[1] = (float)(-(((double)row - H * 0.5) / focal));
+    } else {
+      const float f = (float)focal;
+      cam[0] = ((float)col - W * 0.5f) / f;
+      cam[1] = -(((float)row - H * 0.5f) / f);
+    }
+    cam[2] = -1.f;
+    float d[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      float s = fmul_rn(cam[0], c2w[4 * a + 0]);
+      s = fadd_rn(s, fmul_rn(cam[1], c2w[4 * a + 1]));
+      s = fadd_rn(s, fmul_rn(-1.f, c2w[4 * a + 2]));
+      d[a] = s;
+    }
+    const double nrm = (double)sqrtf(__builtin_fmaf(d[2], d[2], __builtin_fmaf(d[1], d[1], fmul_rn(d[0], d[0]))));
+    double v[3], gv[3], dot = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      v[a] = (double)d[a] / nrm;
+      gv[a] = (double)dvd[3 * p + a];
+      dot += v[a] * gv[a];
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const double g = (gv[a] - v[a] * dot) / nrm;
+#pragma unroll
+      for (int b = 0; b < 3; ++b) t[4 * a + b] = g * (double)cam[b];
+      t[4 * a + 3] = (double)dro[3 * p + a];
+    }
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) {
+    double s = t[i];
+#pragma unroll
+    for (int k = 32; k > 0; k >>= 1) s += shfl_xor_d(s, k);
+    if (lane == 0) red[w][i] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < 12) {
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < kRaysBwdBlock / 64; ++k) s += red[k][threadIdx.x];
+    part[(size_t)blockIdx.x * 12 + threadIdx.x] = s;
+  }
+}
+
+__global__ __launch_bounds__(kRaysBwdBlock) void get_rays_bwd_final_kernel(const double* __restrict__ part,
+                                                                           int nblocks, float* __restrict__ dc2w) {
+  __shared__ double red[kRaysBwdBlock / 64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (int i = 0; i < 12; ++i) {
+    double s = 0.0;
+    for (int b = threadIdx.x; b < nblocks; b += kRaysBwdBlock) s += part[(size_t)b * 12 + i];
+#pragma unroll
+    for (int k = 32; k > 0; k >>= 1) s += shfl_xor_d(s, k);
+    if (lane == 0) red[w] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double tot = 0.0;
+#pragma unroll
+      for (int k = 0; k < kRaysBwdBlock / 64; ++k) tot += red[k];
+      dc2w[i] = (float)tot;
+    }
+    __syncthreads();
+  }
+}
+
 // ---------------------------------------------------------------- scans
 CN_DEV double shfl_up_d(double v, int k) {
   const int lo = __shfl_up(__double2loint(v), k);

@@ -136,13 +136,41 @@ class Engine:
     def new_act(self, M):
         return torch.empty(self.act_bytes(M), dtype=torch.uint8, device=self.device)
 
-    def mlp_bwd(self, blob, M, dsigma, drgb, act, codes=False, act_M=0, row0=0):
+    def mlp_bwd(self, blob, M, dsigma, drgb, act, codes=False, act_M=0, row0=0, pose=False):
         """dX chain over rows [row0, row0 + pad(M)) of an act_M-sample workspace
         (act_M 0: M); dsigma / drgb hold the range's rows.  codes: the
-        codes-only variant (stores only the planes mlp_dbias reads)."""
-        fn = self.L.cn_mlp_bwd_codes if codes else self.L.cn_mlp_bwd_rows
+        codes-only variant (stores only the planes mlp_dbias reads).  pose:
+        the codes-only variant that also stores the two input-side gradient
+        planes mlp_input_grad reads (cn_mlp_bwd_pose)."""
+        fn = self.L.cn_mlp_bwd_pose if pose else self.L.cn_mlp_bwd_codes if codes else self.L.cn_mlp_bwd_rows
         check(fn(self._plan, ptr(self.pack_bwd), ptr(blob), M, ptr(dsigma), ptr(drgb), ptr(act), int(act_M),
                  int(row0), self.stream), "cn_mlp_bwd")
+
+    def mlp_input_grad(self, act, M, xyz=None, viewdir=None, rays_o=None, rays_d=None, z=None, z_stride=0,
+                       n_samples=0, act_M=0, row0=0, params=None, per_ray=True):
+        """Gradient with respect to the network inputs over rows [row0, row0 +
+        pad(M)), after mlp_bwd(pose=True) or the training backward over the
+        same rows; the inputs are the forward's (points or rays x z).
+        -> (d_xyz [Mp,3], d_viewdir [Mp,3]) and, in ray mode with per_ray,
+        (d_rays_o [R,3], d_rays_d [R,3]); ``params``: tensors or a table,
+        default the parameters of the last ensure_packed."""
+        ptab = self._param_tab if params is None else (
+            params if isinstance(params, torch.Tensor) else self.table(params))
+        if ptab is None:
+            raise RuntimeError("mlp_input_grad: no packed weights (call ensure_packed before the forward)")
+        Mp = self.pad(M)
+        dxyz = torch.empty(Mp, 3, dtype=torch.float32, device=self.device)
+        dvd = torch.empty(Mp, 3, dtype=torch.float32, device=self.device)
+        dro = drd = None
+        if xyz is None and per_ray:
+            R = M // max(1, int(n_samples))
+            dro = torch.empty(R, 3, dtype=torch.float32, device=self.device)
+            drd = torch.empty(R, 3, dtype=torch.float32, device=self.device)
+        check(self.L.cn_mlp_input_grad(self._plan, ptr(ptab), ptr(act), int(act_M), int(row0), M, ptr(xyz),
+                                       ptr(viewdir), ptr(rays_o), ptr(rays_d), ptr(z), int(z_stride),
+                                       int(n_samples), ptr(dxyz), ptr(dvd), ptr(dro), ptr(drd), self.stream),
+              "cn_mlp_input_grad")
+        return dxyz, dvd, dro, drd
 
     def mlp_dw(self, act, M, zvec, grads, dbuf, ws=None, act_M=0, row0=0, db_accum=False, nwg=0, params=None):
         """Weight gradients over rows [row0, row0 + pad(M)) (grads accumulate;
@@ -259,6 +287,17 @@ def get_rays_dev(H, W, focal, focal_is_f64, c2w):
     check(L.cn_get_rays(H, W, float(focal), int(focal_is_f64), ptr(c2w), ptr(ro), ptr(vd), _dev_stream(c2w)),
           "cn_get_rays")
     return ro, vd
+
+
+def get_rays_bwd(H, W, focal, focal_is_f64, c2w, d_rays_o, d_viewdirs):
+    """Gradient of get_rays_dev's outputs with respect to c2w -> (3, 4)."""
+    L = _lib.lib()
+    dev = c2w.device
+    out = torch.empty(3, 4, dtype=torch.float32, device=dev)
+    ws = torch.empty(L.cn_get_rays_bwd_ws_bytes(H, W), dtype=torch.uint8, device=dev)
+    check(L.cn_get_rays_bwd(H, W, float(focal), int(focal_is_f64), ptr(c2w), ptr(d_rays_o), ptr(d_viewdirs),
+                            ptr(out), ptr(ws), _dev_stream(c2w)), "cn_get_rays_bwd")
+    return out
 
 
 def sample_points(ro, vd, z, R, N):

@@ -34,6 +34,7 @@ from .data import SRN, collate_one
 from .metrics import ssim_legacy
 from .model import CodeNeRF
 from .optim import FusedAdamW
+from .pose import PoseParam, perturb_pose
 from .render import ImageStep
 from .trainer import load_hpams
 from .utils import get_rays, image_float_to_uint8
@@ -65,7 +66,20 @@ class Optimizer:
         z += torch.rand(N) * (far - near) / (2 * N)
         return z.to(self.device)
 
-    def optimize_objs(self, instance_ids, lr=1e-2, lr_half_interval=50, save_img=True):
+    def optimize_objs(self, instance_ids, lr=1e-2, lr_half_interval=50, save_img=True, optimize_pose=False,
+                      pose_lr=1e-3, pose_noise=None):
+        """optimize_pose (no reference counterpart): every target view's
+        camera pose is refined together with the codes -- one ``PoseParam``
+        per view, started at the dataset pose (SRN ships ground-truth poses,
+        so ``pose_noise = (rotation in degrees, translation[, seed])``
+        perturbs the start), each in an AdamW group of its own at ``pose_lr``,
+        halved on the codes' schedule.  codes.pth then also holds
+        ``optimized_poses`` and the per-view rotation (degrees) / translation
+        error against the dataset pose.  Off: exactly the reference loop."""
+        self.optimize_pose = bool(optimize_pose)
+        self.pose_lr = float(pose_lr)
+        self.pose_params = []
+        self.optimized_poses, self.pose_rot_err, self.pose_trans_err = {}, {}, {}
         if self.rank == 0:
             with open(os.path.join(self.save_dir, "opt_hpams.json"), "w") as f:
                 json.dump({"instance_ids": list(map(int, instance_ids)), "lr": lr,
@@ -81,17 +95,30 @@ class Optimizer:
             self.nopts = 0
             shapecode = self.mean_shape.to(self.device).clone().detach().requires_grad_()
             texturecode = self.mean_texture.to(self.device).clone().detach().requires_grad_()
+            if self.optimize_pose:
+                self.pose_params = [self._start_pose(poses[0, iid], pose_noise, num)
+                                    for num, iid in enumerate(instance_ids)]
             self.set_optimizers(shapecode, texturecode)
             while self.nopts < self.num_opts:
                 shapecode.grad = torch.zeros_like(shapecode)
                 texturecode.grad = torch.zeros_like(texturecode)
+                for pp in self.pose_params:
+                    pp.delta.grad = torch.zeros_like(pp.delta)
                 t1 = time.time()
                 gens, gts = [], []
                 for num, iid in enumerate(instance_ids):
                     tgt_img = imgs[0, iid].reshape(-1, 3).to(self.device)
-                    rays_o, viewdir = get_rays(H, W, focal, poses[0, iid])
-                    losses, rgb, reg = self.step_impl.forward_backward(
-                        rays_o, viewdir, self._z_vals(), tgt_img, shapecode, texturecode, 0, weight_grads=False)
+                    if self.optimize_pose:
+                        pp = self.pose_params[num]
+                        rays_o, viewdir = pp.rays(H, W, focal)
+                        losses, rgb, reg = self.step_impl.forward_backward(
+                            rays_o, viewdir, self._z_vals(), tgt_img, shapecode, texturecode, 0, weight_grads=False,
+                            input_grads=True)
+                        pp.backward_from_ray_grads(self.step_impl.last_ray_grads)
+                    else:
+                        rays_o, viewdir = get_rays(H, W, focal, poses[0, iid])
+                        losses, rgb, reg = self.step_impl.forward_backward(
+                            rays_o, viewdir, self._z_vals(), tgt_img, shapecode, texturecode, 0, weight_grads=False)
                     gens.append(rgb.reshape(H, W, 3))
                     gts.append(tgt_img.reshape(H, W, 3))
                 self.opts.step()
@@ -125,11 +152,32 @@ class Optimizer:
                     self.ssim_eval.setdefault(num_obj, []).append(ssim)
             self.optimized_shapecodes[num_obj] = shapecode.detach().cpu()
             self.optimized_texturecodes[num_obj] = texturecode.detach().cpu()
+            if self.optimize_pose:
+                errs = [pp.errors(poses[0, iid]) for pp, iid in zip(self.pose_params, instance_ids)]
+                with torch.no_grad():
+                    self.optimized_poses[num_obj] = torch.stack([pp.c2w().cpu() for pp in self.pose_params])
+                self.pose_rot_err[num_obj] = [e[0] for e in errs]
+                self.pose_trans_err[num_obj] = [e[1] for e in errs]
             self.save_opts(num_obj)
 
+    def _start_pose(self, c2w, pose_noise, view):
+        """PoseParam of one target view: the dataset pose, perturbed by
+        pose_noise = (degrees, translation[, seed]) (seed + view index)."""
+        c = c2w.reshape(4, 4).to(torch.float32)
+        if pose_noise is not None:
+            deg, trans = float(pose_noise[0]), float(pose_noise[1])
+            seed = int(pose_noise[2]) if len(pose_noise) > 2 else 0
+            c = perturb_pose(c, deg, trans, seed + view)
+        return PoseParam(c.to(self.device))
+
     def set_optimizers(self, shapecode, texturecode):
-        lr = self.lr * 2 ** (-(self.nopts // self.lr_half_interval))
-        self.opts = FusedAdamW([{"params": [shapecode], "lr": lr}, {"params": [texturecode], "lr": lr}])
+        k = 2 ** (-(self.nopts // self.lr_half_interval))
+        lr = self.lr * k
+        groups = [{"params": [shapecode], "lr": lr}, {"params": [texturecode], "lr": lr}]
+        # pose refinement: one group per view, no decay (it would pull the pose back to its start)
+        groups += [{"params": [pp.delta], "lr": self.pose_lr * k, "weight_decay": 0.0}
+                   for pp in getattr(self, "pose_params", [])]
+        self.opts = FusedAdamW(groups)
 
     def log_opt_psnr(self, mse, time_spent, num_obj):
         self.psnr_opt.setdefault(num_obj, []).append(float(-10 * np.log(mse) / np.log(10)))
@@ -140,11 +188,19 @@ class Optimizer:
     def save_opts(self, num_obj):
         if self.rank != 0:
             return
-        torch.save({"ids": [str(i) for i in self.ids], "num_obj": num_obj,
-                    "optimized_shapecodes": self.optimized_shapecodes,
-                    "optimized_texturecodes": self.optimized_texturecodes,
-                    "psnr_eval": self.psnr_eval, "ssim_eval": self.ssim_eval},
-                   os.path.join(self.save_dir, "codes.pth"))
+        torch.save(self.saved_dict(num_obj), os.path.join(self.save_dir, "codes.pth"))
+
+    def saved_dict(self, num_obj):
+        """codes.pth: the reference's keys (src/optimizer.py:138-145); pose
+        refinement adds its own and nothing when it is off."""
+        d = {"ids": [str(i) for i in self.ids], "num_obj": num_obj,
+             "optimized_shapecodes": self.optimized_shapecodes,
+             "optimized_texturecodes": self.optimized_texturecodes,
+             "psnr_eval": self.psnr_eval, "ssim_eval": self.ssim_eval}
+        if getattr(self, "optimize_pose", False):
+            d.update(optimized_poses=self.optimized_poses, pose_rot_err_deg=self.pose_rot_err,
+                     pose_trans_err=self.pose_trans_err)
+        return d
 
     def save_img(self, generated_imgs, gt_imgs, obj_id, instance_num, opt=True):
         from PIL import Image

@@ -47,6 +47,7 @@ class ImageStep:
         # store-vs-recompute A/B (fine step only): the loss forwards store no
         # dW operand planes; a second forward writes them before the backward
         self.recompute = False
+        self.last_ray_grads = None               # forward_backward(input_grads=True)
         self._ws = {}                            # device -> grow-only workspace
         self._side = {}                          # device -> side stream
         # called whenever a step starts writing .grad (dp.GradExchange's
@@ -180,28 +181,39 @@ class ImageStep:
 
     # ------------------------------------------------------------ steps
     def forward_backward(self, rays_o, viewdirs, z_vals, gt, shape_table, texture_table, obj_idx,
-                         reg=True, weight_grads=True):
+                         reg=True, weight_grads=True, input_grads=False):
         """One image: returns (chunk losses [ceil(R/chunk)], rendered rgb [R,3],
         reg loss [1]).  Gradients are accumulated into .grad.  weight_grads
         False (codes-only optimisation, src/optimizer.py): the weight-gradient
-        pass is replaced by the bias sums the code gradients need."""
+        pass is replaced by the bias sums the code gradients need.
+        input_grads (pose refinement; no reference counterpart): the gradient
+        of the summed chunk losses with respect to every ray is left in
+        ``self.last_ray_grads = (d_rays_o [R,3], d_viewdirs [R,3])`` (the
+        codes path then runs the backward that also stores the two input-side
+        gradient planes); the return value is unchanged."""
         eng = self.model.engine()
         R = rays_o.shape[0]
         N = z_vals.shape[-1]
         z = z_vals.contiguous().to(eng.device, torch.float32)
-        losses, rgbs, regs = [], [], []
+        losses, rgbs, regs, ray_grads = [], [], [], []
         for k, (a, b) in enumerate(self.ray_parts(eng, R, N)):
             zp = z if z.dim() == 1 else z[a:b]
             l, c, r = self._coarse_part(eng, rays_o[a:b], viewdirs[a:b], zp, gt[a:b], shape_table, texture_table,
-                                        obj_idx, reg and k == 0, weight_grads)
+                                        obj_idx, reg and k == 0, weight_grads, input_grads)
             losses.append(l)
             rgbs.append(c)
             regs.append(r)
+            if input_grads:
+                ray_grads.append(self._part_ray_grads)
+        if input_grads:
+            self.last_ray_grads = ray_grads[0] if len(ray_grads) == 1 else (
+                torch.cat([g[0] for g in ray_grads]), torch.cat([g[1] for g in ray_grads]))
         if len(losses) == 1:
             return losses[0], rgbs[0], regs[0]
         return torch.cat(losses), torch.cat(rgbs), regs[0]
 
-    def _coarse_part(self, eng, rays_o, viewdirs, z, gt, shape_table, texture_table, obj_idx, reg, weight_grads):
+    def _coarse_part(self, eng, rays_o, viewdirs, z, gt, shape_table, texture_table, obj_idx, reg, weight_grads,
+                     input_grads=False):
         params = self.model.param_list()
         grads = self.ensure_grads(params)
         self.ensure_grads([shape_table, texture_table])
@@ -231,7 +243,7 @@ class ImageStep:
             self._bwd_dw(eng, blob, ws, zvec, eng.table(grads), M)
         else:
             ev = tm.mark("bwd") if tm else None
-            eng.mlp_bwd(blob, M, dsig, drgb, ws["act"], codes=True, act_M=cap, row0=0)
+            eng.mlp_bwd(blob, M, dsig, drgb, ws["act"], codes=True, act_M=cap, row0=0, pose=input_grads)
             if tm:
                 tm.done("bwd", ev, n=M)
                 ev = tm.mark("dw")
@@ -239,6 +251,12 @@ class ImageStep:
             if tm:
                 tm.done("dw", ev, n=M)
             grads = ws.setdefault("scratch_grads", [torch.zeros_like(p) for p in params])
+        if input_grads:
+            # both backwards left dA of encoding_xyz and of encoding_viewdir in
+            # the workspace; the ray direction is also the view direction
+            _, _, d_ro, d_rd = eng.mlp_input_grad(ws["act"], M, rays_o=rays_o, rays_d=viewdirs, z=z,
+                                                  z_stride=z_stride, n_samples=N, act_M=cap, row0=0)
+            self._part_ray_grads = (d_ro, d_rd)
         reg_out = torch.empty(1, dtype=torch.float32, device=eng.device)     # written by cn_latent_bwd
         eng.latent_bwd(params, grads, s, t, zvec, ws["dbuf"], shape_table.grad[obj_idx],
                        texture_table.grad[obj_idx], self.reg_coef if reg else 0.0, reg_out)

@@ -26,11 +26,32 @@ def _device():
     return torch.device("cuda", torch.cuda.current_device())
 
 
+class _GetRays(torch.autograd.Function):
+    """get_rays with a backward into c2w (cn_get_rays_bwd): pose refinement."""
+
+    @staticmethod
+    def forward(ctx, m, H, W, fval, f64):
+        ctx.save_for_backward(m)
+        ctx.cam = (H, W, fval, f64)
+        return _eng.get_rays_dev(H, W, fval, f64, m)
+
+    @staticmethod
+    def backward(ctx, g_ro, g_vd):
+        (m,) = ctx.saved_tensors
+        H, W, fval, f64 = ctx.cam
+        zeros = lambda: torch.zeros(H * W, 3, dtype=torch.float32, device=m.device)
+        g_ro = zeros() if g_ro is None else g_ro.contiguous().to(torch.float32)
+        g_vd = zeros() if g_vd is None else g_vd.contiguous().to(torch.float32)
+        d = _eng.get_rays_bwd(H, W, fval, f64, m, g_ro, g_vd)
+        return torch.cat([d, torch.zeros(1, 4, dtype=torch.float32, device=m.device)]), None, None, None, None
+
+
 def get_rays(H, W, focal, c2w):
     """Pinhole rays, OpenGL camera convention, principal point (W/2, H/2),
     no half-pixel offset.  ``focal`` as a float64 tensor (what default_collate
     yields) makes the camera directions float64 before the cast, like the
-    reference's type promotion."""
+    reference's type promotion.  A ``c2w`` that requires grad gets its
+    gradient from the HIP backward of the ray generation."""
     dev = c2w.device if c2w.is_cuda else _device()
     if isinstance(focal, torch.Tensor):
         f64 = focal.dtype == torch.float64
@@ -38,6 +59,8 @@ def get_rays(H, W, focal, c2w):
     else:
         f64, fval = False, float(focal)
     m = c2w.reshape(-1, 4, 4)[0, :4, :4].to(dev, torch.float32).contiguous()
+    if m.requires_grad:
+        return _GetRays.apply(m, int(H), int(W), fval, f64)
     return _eng.get_rays_dev(int(H), int(W), fval, f64, m)
 
 

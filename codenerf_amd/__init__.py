@@ -11,5 +11,6 @@ import os as _os
 __path__ = [_os.path.join(_os.path.dirname(_os.path.dirname(_os.path.abspath(__file__))), "code-nerf_amd")]
 
 from ._lib import CnError, HipUnavailable, LIB_PATH  # noqa: E402,F401
+from .pose import PoseParam  # noqa: E402,F401
 
-__all__ = ["HipUnavailable", "CnError", "LIB_PATH"]
+__all__ = ["HipUnavailable", "CnError", "LIB_PATH", "PoseParam"]

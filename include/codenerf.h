@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CN_ABI_VERSION 3
+#define CN_ABI_VERSION 4
 #define CN_FP32 0 /* exact-fp32 MFMA path (parity) */
 #define CN_BF16 1 /* bf16 operands, fp32 accumulate (throughput) */
 /* error-compensated bf16: weights and chain operands as bf16 hi + lo pairs,
@@ -167,6 +167,34 @@ int cn_mlp_bwd_codes(const cn_plan *plan, const void *d_pack_bwd, const float *d
                      const float *d_dsigma, const float *d_drgb, void *d_act, int act_M,
                      int act_row0, void *stream);
 
+/* ---- camera-pose refinement (no reference counterpart; ABI 4: the reference
+ * lists "Pose Optimizing" as not done).  cn_mlp_bwd_pose: the backward of a
+ * cn_mlp_fwd_codes forward, same arguments as cn_mlp_bwd_codes; it stores what
+ * that call stores plus the two input-side gradient planes cn_mlp_input_grad
+ * reads (dA of encoding_xyz and of encoding_viewdir).  The training backward
+ * (cn_mlp_bwd / cn_mlp_bwd_rows) stores both planes too. */
+int cn_mlp_bwd_pose(const cn_plan *plan, const void *d_pack_bwd, const float *d_blob, int M,
+                    const float *d_dsigma, const float *d_drgb, void *d_act, int act_M,
+                    int act_row0, void *stream);
+
+/* ---- gradient with respect to the network inputs (no reference counterpart;
+ * the autograd of src/model.py:4-7,38,47 restated), for rows [act_row0,
+ * act_row0 + pad(M)) of a workspace laid out for act_M samples (act_M <= 0: M)
+ * after cn_mlp_bwd_pose or cn_mlp_bwd_rows over the same rows.  The inputs are
+ * those of the forward: mode A (d_xyz != NULL) or mode B exactly as cn_mlp_fwd
+ * selects them.  d_params: the parameter tensors the forward used.
+ * d_dxyz, d_dviewdir [Mp][3] are written (rows >= M as 0); -grad sigma of a
+ * sample is its surface normal.  Mode B, optional (both or none; NULL in mode
+ * A): d_drays_o [R][3] = sum_s d_xyz and d_drays_d [R][3] = sum_s (z_s d_xyz +
+ * d_viewdir) over each ray's n_samples rows, summed in float64 in a fixed
+ * order (deterministic, written).  Returns -1 with cn_last_error() for rows
+ * outside the workspace or act_row0 not a multiple of 256. */
+int cn_mlp_input_grad(const cn_plan *plan, const float *const *d_params, const void *d_act,
+                      int act_M, int act_row0, int M, const float *d_xyz,
+                      const float *d_viewdir, const float *d_rays_o, const float *d_rays_d,
+                      const float *d_z, int z_stride, int n_samples, float *d_dxyz,
+                      float *d_dviewdir, float *d_drays_o, float *d_drays_d, void *stream);
+
 /* ---- weight / bias gradients, accumulated into d_grads; d_dbuf
  * (num_inject x 256) receives this call's bias gradient of every layer fed by
  * a latent code (input of cn_latent_bwd).  d_params: the parameter tensors the
@@ -211,6 +239,16 @@ int cn_latent_bwd(const cn_plan *plan, const float *const *d_params, float *cons
  * the camera directions in float64 (type promotion) before casting. */
 int cn_get_rays(int H, int W, double focal, int focal_is_f64, const float *d_c2w,
                 float *d_rays_o, float *d_viewdirs, void *stream);
+/* autograd of get_rays with respect to c2w (no reference counterpart; ABI 4).
+ * Same (H, W, focal, focal_is_f64, d_c2w) as the forward, plus the gradients
+ * of its outputs [H*W][3]; d_dc2w: 12 floats (3x4 row-major: rotation columns,
+ * then translation), written, not accumulated.  Two-stage float64 sum in a
+ * fixed order (deterministic).  d_ws: cn_get_rays_bwd_ws_bytes(H, W) bytes
+ * (0: H, W invalid). */
+size_t cn_get_rays_bwd_ws_bytes(int H, int W);
+int cn_get_rays_bwd(int H, int W, double focal, int focal_is_f64, const float *d_c2w,
+                    const float *d_drays_o, const float *d_dviewdirs, float *d_dc2w, void *d_ws,
+                    void *stream);
 /* sample_from_rays point expansion, src/utils.py:30-31 */
 int cn_sample_points(const float *d_rays_o, const float *d_viewdirs, const float *d_z, int z_stride,
                      int R, int N, float *d_xyz, float *d_viewdir_rep, void *stream);

@@ -2,6 +2,11 @@
 
   python optimize.py --saved_dir srncar --tgt_instances 1 [--splits test]
          [--num_opts 200] [--lr 1e-2] [--lr_half_interval 50] [--save_img True]
+         [--optimize_pose True [--pose_lr 1e-3] [--pose_noise_deg 0] [--pose_noise_trans 0]]
+
+--optimize_pose (no reference counterpart) refines every target view's camera
+pose together with the codes; the two noise flags perturb the dataset poses it
+starts from (SRN ships ground-truth poses).
 """
 import argparse
 import os
@@ -11,7 +16,7 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 
 
-def main():
+def build_parser():
     from codenerf_amd.utils import str2bool
     ap = argparse.ArgumentParser(description="CodeNeRF")
     ap.add_argument("--gpu", dest="gpu", default=0)
@@ -24,13 +29,30 @@ def main():
     ap.add_argument("--save_img", dest="save_img", default=True)
     ap.add_argument("--jsonfile", dest="jsonfile", default="srncar.json")
     ap.add_argument("--batchsize", dest="batchsize", default=2048)
-    args = ap.parse_args()
+    ap.add_argument("--optimize_pose", dest="optimize_pose", type=str2bool, default=False,
+                    help="refine the target views' camera poses together with the codes")
+    ap.add_argument("--pose_lr", dest="pose_lr", type=float, default=1e-3)
+    ap.add_argument("--pose_noise_deg", dest="pose_noise_deg", type=float, default=0.0,
+                    help="rotate each starting pose by this many degrees about a seeded axis")
+    ap.add_argument("--pose_noise_trans", dest="pose_noise_trans", type=float, default=0.0,
+                    help="shift each starting pose by this length times a seeded normal vector")
+    return ap
+
+
+def main():
+    from codenerf_amd.utils import str2bool
+    args = build_parser().parse_args()
 
     from codenerf_amd.optimizer import Optimizer
     tgt = [int(i) for i in args.tgt_instances]
     opt = Optimizer(args.saved_dir, int(args.gpu), tgt, args.splits, args.jsonfile, int(args.batchsize),
                     int(args.num_opts))
-    opt.optimize_objs(tgt, float(args.lr), int(args.lr_half_interval), str2bool(args.save_img))
+    if args.optimize_pose:
+        noise = (args.pose_noise_deg, args.pose_noise_trans) if args.pose_noise_deg or args.pose_noise_trans else None
+        opt.optimize_objs(tgt, float(args.lr), int(args.lr_half_interval), str2bool(args.save_img),
+                          optimize_pose=True, pose_lr=args.pose_lr, pose_noise=noise)
+    else:
+        opt.optimize_objs(tgt, float(args.lr), int(args.lr_half_interval), str2bool(args.save_img))
 
 
 if __name__ == "__main__":
