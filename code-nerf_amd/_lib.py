@@ -79,6 +79,7 @@ _SIGS = {
     "cn_sample_pdf": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P]),
     "cn_render_loss_fine": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P,
                                  _P]),
+    "cn_composite_fine_fwd": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "cn_adamw_step": (_I, [_I, _P, _P, _P, _P, _P, _P, _D, _D, _D, _D, _I, _P]),
     "cn_adamw_step_zero_grad": (_I, [_I, _P, _P, _P, _P, _P, _P, _D, _D, _D, _D, _I, _P]),
     "cn_clock_probe": (_I, [_P, _I, _I, ctypes.c_uint, _P]),

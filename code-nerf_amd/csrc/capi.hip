@@ -603,6 +603,20 @@ int cn_render_loss_fine(const float* d_sigma_c, const float* d_rgb_c, const floa
   return launch_check("chunk_loss_kernel");
 }
 
+int cn_composite_fine_fwd(const float* d_sigma_c, const float* d_rgb_c, const float* d_z_c, int zc_stride, int Nc,
+                          const float* d_sigma_f, const float* d_rgb_f, const float* d_z_f, int Nf, int R,
+                          int white_bg, float* d_out_rgb, float* d_out_depth, float* d_out_acc, void* stream) {
+  if (!d_sigma_c || !d_rgb_c || !d_z_c || !d_sigma_f || !d_rgb_f || !d_z_f || !d_out_rgb || !d_out_depth)
+    return fail("cn_composite_fine_fwd: NULL argument");
+  if (Nc <= 0 || Nf <= 0) return fail("cn_composite_fine_fwd: Nc and Nf must be positive");
+  if (check_rn(R, Nc + Nf, "cn_composite_fine_fwd")) return -1;
+  if (zc_stride != 0 && zc_stride != Nc) return fail("cn_composite_fine_fwd: zc_stride must be 0 or Nc");
+  hipLaunchKernelGGL(composite_fine_fwd_kernel, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), d_sigma_c, d_rgb_c,
+                     d_z_c, zc_stride, Nc, d_sigma_f, d_rgb_f, d_z_f, Nf, R, white_bg, d_out_rgb, d_out_depth,
+                     d_out_acc);
+  return launch_check("composite_fine_fwd_kernel");
+}
+
 static int adamw_impl(int nseg, float* const* p, float* const* g, float* const* m, float* const* v, const int* n,
                       const double* lr, double wd, double beta1, double beta2, double eps, int step, int zero_grad,
                       void* stream) {

@@ -554,6 +554,69 @@ __global__ __launch_bounds__(256) void fine_render_loss_kernel(
   }
 }
 
+// Forward half of fine_render_loss_kernel (test-time rendering): the same
+// merge, ray_forward and ray_reduce, so the rgb comes out bit for bit as the
+// loss kernel's; plus depth and, when out_acc is given, the weight sum.  No
+// gt, no gradients, no scatter table: an unwritten merged slot (non-finite z)
+// is only ever read, from LDS.
+__global__ __launch_bounds__(256) void composite_fine_fwd_kernel(
+    const float* __restrict__ sig_c, const float* __restrict__ rgb_c, const float* __restrict__ zc, int zc_stride,
+    int Nc, const float* __restrict__ sig_f, const float* __restrict__ rgb_f, const float* __restrict__ zf, int Nf,
+    int R, int white_bg, float* __restrict__ out_rgb, float* __restrict__ out_depth, float* __restrict__ out_acc) {
+  __shared__ float m_sig[4][kMaxRaySamples], m_z[4][kMaxRaySamples], m_rgb[4][kMaxRaySamples * 3];
+  __shared__ float z_stage[4][kMaxRaySamples];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + wv;
+  if (r >= R) return;                       // wave-uniform; only wave-level sync below
+  const int N = Nc + Nf;
+  const float* zcr = zc + (size_t)r * zc_stride;
+  const float* zfr = zf + (size_t)r * Nf;
+  auto wave_sync = [] {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  };
+  float* zs = z_stage[wv];
+  for (int i = lane; i < Nc; i += 64) zs[i] = zcr[i];
+  for (int j = lane; j < Nf; j += 64) zs[Nc + j] = zfr[j];
+  wave_sync();
+  // merged position = own index + number of the other list's samples before it
+  for (int i = lane; i < Nc; i += 64) {
+    const float v = zs[i];
+    int lo = 0, hi = Nf;                    // count zf < v
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (zs[Nc + mid] < v) lo = mid + 1; else hi = mid; }
+    const int p = i + lo;
+    const size_t g = (size_t)r * Nc + i;
+    m_sig[wv][p] = sig_c[g];
+    m_z[wv][p] = v;
+    m_rgb[wv][3 * p + 0] = rgb_c[3 * g + 0];
+    m_rgb[wv][3 * p + 1] = rgb_c[3 * g + 1];
+    m_rgb[wv][3 * p + 2] = rgb_c[3 * g + 2];
+  }
+  for (int j = lane; j < Nf; j += 64) {
+    const float v = zs[Nc + j];
+    int lo = 0, hi = Nc;                    // count zc <= v
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (zs[mid] <= v) lo = mid + 1; else hi = mid; }
+    const int p = j + lo;
+    const size_t g = (size_t)r * Nf + j;
+    m_sig[wv][p] = sig_f[g];
+    m_z[wv][p] = v;
+    m_rgb[wv][3 * p + 0] = rgb_f[3 * g + 0];
+    m_rgb[wv][3 * p + 1] = rgb_f[3 * g + 1];
+    m_rgb[wv][3 * p + 2] = rgb_f[3 * g + 2];
+  }
+  wave_sync();
+  RayState st;
+  ray_forward(st, m_sig[wv], m_rgb[wv], m_z[wv], N);
+  float o[5];
+  ray_reduce(st, o);
+  if (lane == 0) {
+    for (int c = 0; c < 3; ++c) out_rgb[3 * r + c] = white_bg ? fadd_rn(o[c] + 1.f, -o[4]) : o[c];
+    out_depth[r] = o[3];
+    if (out_acc) out_acc[r] = o[4];
+  }
+}
+
 // ---------------------------------------------------------------- misc
 __global__ __launch_bounds__(256) void stratified_points_kernel(const float* __restrict__ ro, const float* __restrict__ vd,
                                                                 const float* __restrict__ z, int z_stride, int R, int N,

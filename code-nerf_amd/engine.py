@@ -279,6 +279,21 @@ def render_loss_fine(sigma_c, rgb_c, z_c, Nc, sigma_f, rgb_f, z_f, Nf, R, gt, ch
     return out_rgb, chunk_loss
 
 
+def composite_fine_fwd(sigma_c, rgb_c, z_c, Nc, sigma_f, rgb_f, z_f, Nf, R, white_bg=True, acc=False):
+    """Forward-only composite over the merged coarse + fine samples (the
+    forward half of render_loss_fine).  -> (rgb (R,3), depth (R,)[, acc (R,)])."""
+    L = _lib.lib()
+    dev = sigma_c.device
+    zc_stride = 0 if z_c.numel() == Nc else Nc
+    out_rgb = torch.empty(R, 3, dtype=torch.float32, device=dev)
+    depth = torch.empty(R, dtype=torch.float32, device=dev)
+    out_acc = torch.empty(R, dtype=torch.float32, device=dev) if acc else None
+    check(L.cn_composite_fine_fwd(ptr(sigma_c), ptr(rgb_c), ptr(z_c), zc_stride, Nc, ptr(sigma_f), ptr(rgb_f),
+                                  ptr(z_f), Nf, R, int(white_bg), ptr(out_rgb), ptr(depth), ptr(out_acc),
+                                  _dev_stream(sigma_c)), "cn_composite_fine_fwd")
+    return (out_rgb, depth, out_acc) if acc else (out_rgb, depth)
+
+
 def get_rays_dev(H, W, focal, focal_is_f64, c2w):
     L = _lib.lib()
     dev = c2w.device

@@ -17,6 +17,12 @@ save_img)``) and loop semantics:
     (dp.gather_by_key), the z jitter of every view drawn first in view order
     so a split changes no draw;
   * ``codes.pth`` with the reference's keys (:138-145).
+With ``N_importance`` > 0 in the JSON (or ``n_importance=``; no reference
+counterpart) the steps and the evaluation run the coarse + fine renderer the
+model was trained with: ``ImageStep.forward_backward_fine(weight_grads=False)``
+with fresh fine draws per view and step, the logged PSNR and the saved image
+from the fine composite, and ``ImageStep.render_fine`` with its deterministic
+fine samples for the evaluation views.  At 0 nothing below changes.
 The model weights are fixed, so the weight-gradient pass is skipped (only the
 dX chain and the code gradients run).  SSIM is ``metrics.ssim_legacy`` -- a
 restatement of skimage's ``structural_similarity(multichannel=True)`` as the
@@ -42,8 +48,11 @@ from .utils import get_rays, image_float_to_uint8
 
 class Optimizer:
     def __init__(self, saved_dir, gpu=0, instance_ids=(), splits="test", jsonfile="srncar.json",
-                 batch_size=2048, num_opts=200, hpams=None, exp_root="exps", dist=None):
+                 batch_size=2048, num_opts=200, hpams=None, exp_root="exps", dist=None, n_importance=None):
         self.hpams = hpams if hpams is not None else load_hpams(jsonfile)
+        # fine samples per ray (the JSON's N_importance, as Trainer reads it;
+        # n_importance overrides it); 0: the reference's coarse-only loop
+        self.n_fine = int(self.hpams.get("N_importance", 0) if n_importance is None else n_importance)
         self.device = torch.device("cuda", int(gpu))
         torch.cuda.set_device(self.device)
         self.exp_root = exp_root
@@ -108,7 +117,19 @@ class Optimizer:
                 gens, gts = [], []
                 for num, iid in enumerate(instance_ids):
                     tgt_img = imgs[0, iid].reshape(-1, 3).to(self.device)
-                    if self.optimize_pose:
+                    if self.n_fine > 0:
+                        # the coarse + fine step the model was trained with,
+                        # codes only; the logged loss and the image are the fine ones
+                        pp = self.pose_params[num] if self.optimize_pose else None
+                        rays_o, viewdir = pp.rays(H, W, focal) if pp else get_rays(H, W, focal, poses[0, iid])
+                        z_c = self._z_vals()
+                        rand_f = torch.rand(H * W, self.n_fine, device=self.device)
+                        _, losses, rgb, reg = self.step_impl.forward_backward_fine(
+                            rays_o, viewdir, z_c, rand_f, tgt_img, shapecode, texturecode, 0, weight_grads=False,
+                            input_grads=self.optimize_pose)
+                        if pp:
+                            pp.backward_from_ray_grads(self.step_impl.last_ray_grads)
+                    elif self.optimize_pose:
                         pp = self.pose_params[num]
                         rays_o, viewdir = pp.rays(H, W, focal)
                         losses, rgb, reg = self.step_impl.forward_backward(
@@ -138,7 +159,12 @@ class Optimizer:
                 for num in dp.shard(views, self.dist):
                     tgt_img = imgs[0, num].reshape(-1, 3).to(self.device)
                     rays_o, viewdir = get_rays(H, W, focal, poses[0, num])
-                    rgb, _ = self.step_impl.render(rays_o, viewdir, zs[num], shapecode, texturecode)
+                    if self.n_fine > 0:
+                        # deterministic fine samples: the split changes no result
+                        rgb, _ = self.step_impl.render_fine(rays_o, viewdir, zs[num], self.n_fine, shapecode,
+                                                            texturecode)
+                    else:
+                        rgb, _ = self.step_impl.render(rays_o, viewdir, zs[num], shapecode, texturecode)
                     se = ((rgb - tgt_img) ** 2).sum(-1)
                     chunk_mse = [float(se[i:i + self.B].mean()) / 3 for i in range(0, H * W, self.B)]
                     local[num] = (float(-10 * np.log(float(np.mean(chunk_mse))) / np.log(10)),

@@ -47,7 +47,8 @@ class ImageStep:
         # store-vs-recompute A/B (fine step only): the loss forwards store no
         # dW operand planes; a second forward writes them before the backward
         self.recompute = False
-        self.last_ray_grads = None               # forward_backward(input_grads=True)
+        self.last_ray_grads = None               # forward_backward[_fine](input_grads=True)
+        self.last_z_f = None                     # fine z of the last forward_backward_fine / render_fine
         self._ws = {}                            # device -> grow-only workspace
         self._side = {}                          # device -> side stream
         # called whenever a step starts writing .grad (dp.GradExchange's
@@ -263,7 +264,7 @@ class ImageStep:
         return chunk_loss, out_rgb, reg_out
 
     def forward_backward_fine(self, rays_o, viewdirs, z_c, rand_f, gt, shape_table, texture_table, obj_idx,
-                              reg=True, z_f=None):
+                              reg=True, z_f=None, weight_grads=True, input_grads=False):
         """Coarse + fine image step (the BASELINE configs' "64 + 64"; no
         reference counterpart -- NeRF hierarchical sampling through the one
         CodeNeRF MLP, oracle/ref_cpu.py:fine_image_step).  Loss = coarse
@@ -273,18 +274,34 @@ class ImageStep:
         z_f (R, Nf), optional: fine samples to use instead of sample_pdf's
         (tests replaying one sampling under two precisions); rand_f is then
         only read for Nf.
+        weight_grads False (codes-only optimisation at test time): both
+        forwards store only what the codes backward reads, one codes backward
+        runs over the coarse and fine rows, and the bias sums replace the
+        weight-gradient pass; the model's .grad tensors are not written.
+        input_grads (pose refinement), on either path: the gradient of both
+        losses with respect to every ray is left in ``self.last_ray_grads``
+        as in forward_backward; z_f is a constant of it (no gradient through
+        sample_pdf, as in NeRF and oracle/ref_cpu.py:fine_image_step).
         Returns (coarse chunk losses, fine chunk losses, fine rgb (R,3), reg)."""
+        if self.recompute and not weight_grads:
+            raise ValueError("recompute rebuilds the weight-gradient operands: it has no codes-only form "
+                             "(weight_grads=False)")
         eng = self.model.engine()
         R = rays_o.shape[0]
         Nc, Nf = z_c.shape[-1], rand_f.shape[-1]
         z_c = z_c.contiguous().to(eng.device, torch.float32)
-        outs, zfs = [], []
+        outs, zfs, ray_grads = [], [], []
         for k, (a, b) in enumerate(self.ray_parts(eng, R, Nc + Nf)):
             zp = z_c if z_c.dim() == 1 else z_c[a:b]
             outs.append(self._fine_part(eng, rays_o[a:b], viewdirs[a:b], zp, rand_f[a:b], gt[a:b], shape_table,
                                         texture_table, obj_idx, reg and k == 0,
-                                        None if z_f is None else z_f[a:b].contiguous()))
+                                        None if z_f is None else z_f[a:b].contiguous(), weight_grads, input_grads))
             zfs.append(self.last_z_f)
+            if input_grads:
+                ray_grads.append(self._part_ray_grads)
+        if input_grads:
+            self.last_ray_grads = ray_grads[0] if len(ray_grads) == 1 else (
+                torch.cat([g[0] for g in ray_grads]), torch.cat([g[1] for g in ray_grads]))
         if len(outs) == 1:
             return outs[0]
         self.last_z_f = torch.cat(zfs)
@@ -292,7 +309,7 @@ class ImageStep:
                 outs[0][3])
 
     def _fine_part(self, eng, rays_o, viewdirs, z_c, rand_f, gt, shape_table, texture_table, obj_idx, reg,
-                   z_f=None):
+                   z_f=None, weight_grads=True, input_grads=False):
         params = self.model.param_list()
         grads = self.ensure_grads(params)
         self.ensure_grads([shape_table, texture_table])
@@ -313,9 +330,10 @@ class ImageStep:
         blob, zvec = eng.latent_fwd(params, s, t)
         tm = self.timers
         ev = tm.mark("fwd") if tm else None
-        rc = self.recompute
+        rc = self.recompute or not weight_grads      # both store only the codes forward's planes
+        zc_stride = 0 if z_c.dim() == 1 else Nc
         sig_c, rgb_c = eng.mlp_fwd(blob, Mc, rays_o=rays_o, rays_d=viewdirs, z=z_c,
-                                   z_stride=0 if z_c.dim() == 1 else Nc, n_samples=Nc, act=ws["act"], act_M=cap,
+                                   z_stride=zc_stride, n_samples=Nc, act=ws["act"], act_M=cap,
                                    act_row0=0, sigma=sig[:Mc_p], rgb=rgb[:Mc_p], codes=rc)
         if tm:
             tm.done("fwd", ev, n=Mc)
@@ -334,7 +352,7 @@ class ImageStep:
         out_f, loss_f = _eng.render_loss_fine(sig_c, rgb_c, z_c, Nc, sig_f, rgb_f, z_f, Nf, R, gt, self.chunk,
                                               dsig[:Mc], drgb[:Mc], dsig[Mc_p:Mc_p + Mf],
                                               drgb[Mc_p:Mc_p + Mf], self.white_bg)
-        if rc:
+        if self.recompute:
             # recompute A/B (hard part 2): the forward passes above
             # stored only ReLU masks + sigma pre-activations; the planes the dW
             # pass reads are produced here by a second training forward
@@ -349,7 +367,28 @@ class ImageStep:
                         act_M=cap, act_row0=Mc_p, sigma=ws["dsig_tmp"][Mc_p:Mp], rgb=ws["drgb_tmp"][Mc_p:Mp])
             if tm:
                 tm.done("fwd", ev)
-        self._bwd_dw(eng, blob, ws, zvec, eng.table(grads), M)
+        if weight_grads:
+            self._bwd_dw(eng, blob, ws, zvec, eng.table(grads), M)
+        else:
+            # one codes backward over the coarse rows, the (zero) padding and
+            # the fine rows, then the bias sums the code gradients need
+            ev = tm.mark("bwd") if tm else None
+            eng.mlp_bwd(blob, M, dsig, drgb, ws["act"], codes=True, act_M=cap, row0=0, pose=input_grads)
+            if tm:
+                tm.done("bwd", ev, n=M)
+                ev = tm.mark("dw")
+            eng.mlp_dbias(ws["act"], M, ws["dbuf"], ws["dw"], act_M=cap)
+            if tm:
+                tm.done("dw", ev, n=M)
+            grads = ws.setdefault("scratch_grads", [torch.zeros_like(p) for p in params])
+        if input_grads:
+            # the input-side gradient planes of the coarse rows and of the fine
+            # rows, each reduced over its own samples; z_f is a constant
+            _, _, dro_c, drd_c = eng.mlp_input_grad(ws["act"], Mc, rays_o=rays_o, rays_d=viewdirs, z=z_c,
+                                                    z_stride=zc_stride, n_samples=Nc, act_M=cap, row0=0)
+            _, _, dro_f, drd_f = eng.mlp_input_grad(ws["act"], Mf, rays_o=rays_o, rays_d=viewdirs, z=z_f,
+                                                    z_stride=Nf, n_samples=Nf, act_M=cap, row0=Mc_p)
+            self._part_ray_grads = (dro_c + dro_f, drd_c + drd_f)
         reg_out = torch.empty(1, dtype=torch.float32, device=eng.device)     # written by cn_latent_bwd
         eng.latent_bwd(params, grads, s, t, zvec, ws["dbuf"], shape_table.grad[obj_idx],
                        texture_table.grad[obj_idx], self.reg_coef if reg else 0.0, reg_out)
@@ -380,6 +419,53 @@ class ImageStep:
             depths.append(d)
         if len(rgbs) == 1:
             return rgbs[0], depths[0]
+        return torch.cat(rgbs), torch.cat(depths)
+
+    @torch.no_grad()
+    def render_fine(self, rays_o, viewdirs, z_c, n_fine, shape_code, texture_code, rand_f=None, z_f=None):
+        """Forward only through the coarse + fine renderer the fine step
+        trains (no reference counterpart): coarse pass -> sample_pdf -> fine
+        pass -> composite over the merged samples -> rgb (R,3), depth (R,).
+        rand_f None: the deterministic samples u_j = (j + 0.5) / n_fine
+        (NeRF's test-time convention; nothing is drawn).  z_f (R, n_fine)
+        given: those fine samples, sample_pdf skipped.  The fine z used are
+        left in ``self.last_z_f``.  No workspace; ray parts as in render."""
+        eng = self.model.engine()
+        params = self.model.param_list()
+        R = rays_o.shape[0]
+        Nc, Nf = z_c.shape[-1], int(n_fine)
+        z = z_c.contiguous().to(eng.device, torch.float32)
+        if z_f is not None:
+            z_f = z_f.contiguous().to(eng.device, torch.float32)
+        elif rand_f is not None:
+            rand_f = rand_f.contiguous().to(eng.device, torch.float32)
+        eng.ensure_packed(params, bwd=False)
+        blob, _ = eng.latent_fwd(params, shape_code.reshape(-1).contiguous(), texture_code.reshape(-1).contiguous())
+        per = max(1, (eng.L.cn_max_samples() - 256) // max(Nc, Nf))
+        zc_stride = 0 if z.dim() == 1 else Nc
+        rgbs, depths, zfs = [], [], []
+        for a in range(0, R, per):
+            b = min(a + per, R)
+            n = b - a
+            zp = z if z.dim() == 1 else z[a:b]
+            sig_c, rgb_c = eng.mlp_fwd(blob, n * Nc, rays_o=rays_o[a:b], rays_d=viewdirs[a:b], z=zp,
+                                       z_stride=zc_stride, n_samples=Nc)
+            if z_f is not None:
+                zf = z_f[a:b]
+            else:
+                rnd = (torch.full((n, Nf), 0.5, dtype=torch.float32, device=eng.device) if rand_f is None
+                       else rand_f[a:b])
+                zf = _eng.sample_pdf(sig_c, zp, n, Nc, rnd)
+            sig_f, rgb_f = eng.mlp_fwd(blob, n * Nf, rays_o=rays_o[a:b], rays_d=viewdirs[a:b], z=zf, z_stride=Nf,
+                                       n_samples=Nf)
+            c, d = _eng.composite_fine_fwd(sig_c, rgb_c, zp, Nc, sig_f, rgb_f, zf, Nf, n, self.white_bg)
+            rgbs.append(c)
+            depths.append(d)
+            zfs.append(zf)
+        if len(rgbs) == 1:
+            self.last_z_f = zfs[0]
+            return rgbs[0], depths[0]
+        self.last_z_f = torch.cat(zfs)
         return torch.cat(rgbs), torch.cat(depths)
 
     @torch.no_grad()

@@ -286,6 +286,16 @@ int cn_render_loss_fine(const float *d_sigma_c, const float *d_rgb_c, const floa
                         float *d_dsig_c, float *d_drgb_c, float *d_dsig_f, float *d_drgb_f,
                         void *stream);
 
+/* forward half of cn_render_loss_fine (test-time rendering; additive to ABI
+ * 4): the same merge of each ray's coarse and fine samples (a coarse sample
+ * precedes a fine one at equal z; Nc + Nf <= 256, zc_stride 0 or Nc), so
+ * d_out_rgb [R][3] equals that call's bit for bit; d_out_depth [R] = sum w z
+ * over the merged samples; d_out_acc [R] = sum w, may be NULL. */
+int cn_composite_fine_fwd(const float *d_sigma_c, const float *d_rgb_c, const float *d_z_c,
+                          int zc_stride, int Nc, const float *d_sigma_f, const float *d_rgb_f,
+                          const float *d_z_f, int Nf, int R, int white_bg, float *d_out_rgb,
+                          float *d_out_depth, float *d_out_acc, void *stream);
+
 /* ---- torch.optim.AdamW step (src/trainer.py:116-120) over nseg tensors
  * (host arrays of device pointers), step = 1-based count of this update. */
 int cn_adamw_step(int nseg, float *const *p, const float *const *g, float *const *m,

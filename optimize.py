@@ -3,10 +3,17 @@
   python optimize.py --saved_dir srncar --tgt_instances 1 [--splits test]
          [--num_opts 200] [--lr 1e-2] [--lr_half_interval 50] [--save_img True]
          [--optimize_pose True [--pose_lr 1e-3] [--pose_noise_deg 0] [--pose_noise_trans 0]]
+         [--n_importance N]
 
 --optimize_pose (no reference counterpart) refines every target view's camera
 pose together with the codes; the two noise flags perturb the dataset poses it
 starts from (SRN ships ground-truth poses).
+
+--n_importance sets the fine samples per ray of the hierarchical (coarse +
+fine) renderer; left out, the JSON's ``N_importance`` decides, as in training.
+Above 0 every optimisation step (codes, and poses with --optimize_pose) runs
+through the fine pass and the evaluation views are rendered with it, with the
+deterministic fine samples u_j = (j + 0.5) / N; 0 is the coarse-only loop.
 """
 import argparse
 import os
@@ -36,6 +43,8 @@ def build_parser():
                     help="rotate each starting pose by this many degrees about a seeded axis")
     ap.add_argument("--pose_noise_trans", dest="pose_noise_trans", type=float, default=0.0,
                     help="shift each starting pose by this length times a seeded normal vector")
+    ap.add_argument("--n_importance", dest="n_importance", type=int, default=None,
+                    help="fine samples per ray (default: the JSON's N_importance; 0: coarse only)")
     return ap
 
 
@@ -46,7 +55,7 @@ def main():
     from codenerf_amd.optimizer import Optimizer
     tgt = [int(i) for i in args.tgt_instances]
     opt = Optimizer(args.saved_dir, int(args.gpu), tgt, args.splits, args.jsonfile, int(args.batchsize),
-                    int(args.num_opts))
+                    int(args.num_opts), n_importance=args.n_importance)
     if args.optimize_pose:
         noise = (args.pose_noise_deg, args.pose_noise_trans) if args.pose_noise_deg or args.pose_noise_trans else None
         opt.optimize_objs(tgt, float(args.lr), int(args.lr_half_interval), str2bool(args.save_img),
