@@ -80,6 +80,8 @@ _SIGS = {
     "cn_render_loss_fine": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P,
                                  _P]),
     "cn_composite_fine_fwd": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "cn_image_metrics_ws_bytes": (_Z, [_I, _I, _I, _I]),
+    "cn_image_metrics": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "cn_adamw_step": (_I, [_I, _P, _P, _P, _P, _P, _P, _D, _D, _D, _D, _I, _P]),
     "cn_adamw_step_zero_grad": (_I, [_I, _P, _P, _P, _P, _P, _P, _D, _D, _D, _D, _I, _P]),
     "cn_clock_probe": (_I, [_P, _I, _I, ctypes.c_uint, _P]),

@@ -14,6 +14,7 @@
 #include "dw.hip"
 #include "optim.hip"
 #include "render.hip"
+#include "metrics.hip"
 #include "inputgrad.hip"
 #include "probe.hip"
 
@@ -615,6 +616,34 @@ int cn_composite_fine_fwd(const float* d_sigma_c, const float* d_rgb_c, const fl
                      d_z_c, zc_stride, Nc, d_sigma_f, d_rgb_f, d_z_f, Nf, R, white_bg, d_out_rgb, d_out_depth,
                      d_out_acc);
   return launch_check("composite_fine_fwd_kernel");
+}
+
+// Argument check shared by the size query and the call (no device call).
+static const char* image_metrics_bad(int H, int W, int V, int chunk) {
+  if (H < kMetWin || W < kMetWin) return "H and W must be at least 7 (one 7x7 SSIM window)";
+  if (V < 1) return "V must be at least 1";
+  if (chunk < 1) return "chunk must be at least 1";
+  if ((long long)H * W > CN_MAX_SAMPLES) return "H * W exceeds CN_MAX_SAMPLES";
+  if (V > 65535) return "at most 65535 views per call";
+  return nullptr;
+}
+
+size_t cn_image_metrics_ws_bytes(int H, int W, int V, int chunk) {
+  if (image_metrics_bad(H, W, V, chunk)) return 0;
+  return (size_t)V * metrics_geom(H, W, chunk).parts() * sizeof(double);
+}
+
+int cn_image_metrics(const float* d_img, const float* d_gt, int H, int W, int V, int chunk, double* d_out,
+                     double* d_chunk_mse, void* d_ws, void* stream) {
+  if (const char* bad = image_metrics_bad(H, W, V, chunk)) return fail(std::string("cn_image_metrics: ") + bad);
+  if (!d_img || !d_gt || !d_out || !d_ws) return fail("cn_image_metrics: NULL argument");
+  const MetricsGeom g = metrics_geom(H, W, chunk);
+  hipLaunchKernelGGL(metrics_partial_kernel, dim3(g.parts(), V), dim3(kMetBlock), 0, S(stream), d_img, d_gt, g,
+                     (double*)d_ws);
+  if (launch_check("metrics_partial_kernel")) return -1;
+  hipLaunchKernelGGL(metrics_final_kernel, dim3(V), dim3(kMetBlock), 0, S(stream), (const double*)d_ws, g, d_out,
+                     d_chunk_mse);
+  return launch_check("metrics_final_kernel");
 }
 
 static int adamw_impl(int nseg, float* const* p, float* const* g, float* const* m, float* const* v, const int* n,

@@ -27,6 +27,11 @@ The model weights are fixed, so the weight-gradient pass is skipped (only the
 dX chain and the code gradients run).  SSIM is ``metrics.ssim_legacy`` -- a
 restatement of skimage's ``structural_similarity(multichannel=True)`` as the
 reference calls it (skimage is not installed: parity unpinned).
+``device_metrics=True`` (no reference counterpart) computes each evaluation
+view's chunk-mean MSE and that SSIM with ``metrics.image_metrics`` on the
+device and reads all of an object's views back at once, instead of one host
+synchronisation per chunk, two image copies and a numpy SSIM per view; the
+dictionaries and ``codes.pth`` keep their shape and keys.
 """
 import json
 import os
@@ -37,7 +42,7 @@ import torch
 
 from . import dp
 from .data import SRN, collate_one
-from .metrics import ssim_legacy
+from .metrics import image_metrics, psnr as mse_to_psnr, ssim_legacy
 from .model import CodeNeRF
 from .optim import FusedAdamW
 from .pose import PoseParam, perturb_pose
@@ -48,11 +53,15 @@ from .utils import get_rays, image_float_to_uint8
 
 class Optimizer:
     def __init__(self, saved_dir, gpu=0, instance_ids=(), splits="test", jsonfile="srncar.json",
-                 batch_size=2048, num_opts=200, hpams=None, exp_root="exps", dist=None, n_importance=None):
+                 batch_size=2048, num_opts=200, hpams=None, exp_root="exps", dist=None, n_importance=None,
+                 device_metrics=False):
         self.hpams = hpams if hpams is not None else load_hpams(jsonfile)
         # fine samples per ray (the JSON's N_importance, as Trainer reads it;
         # n_importance overrides it); 0: the reference's coarse-only loop
         self.n_fine = int(self.hpams.get("N_importance", 0) if n_importance is None else n_importance)
+        # evaluation PSNR / SSIM from the device kernel (metrics.image_metrics),
+        # one read-back per object; off: the host loop below, as the reference
+        self.device_metrics = bool(device_metrics)
         self.device = torch.device("cuda", int(gpu))
         torch.cuda.set_device(self.device)
         self.exp_root = exp_root
@@ -156,7 +165,11 @@ class Optimizer:
                 views = [num for num in range(imgs.shape[1]) if num not in instance_ids]
                 zs = {num: self._z_vals() for num in views}
                 local = {}
-                for num in dp.shard(views, self.dist):
+                mine = dp.shard(views, self.dist)
+                if self.device_metrics:
+                    # (mse, ssim) of every local view, read back once after the last
+                    met = torch.empty(len(mine), 2, dtype=torch.float64, device=self.device)
+                for k, num in enumerate(mine):
                     tgt_img = imgs[0, num].reshape(-1, 3).to(self.device)
                     rays_o, viewdir = get_rays(H, W, focal, poses[0, num])
                     if self.n_fine > 0:
@@ -165,14 +178,20 @@ class Optimizer:
                                                             texturecode)
                     else:
                         rgb, _ = self.step_impl.render(rays_o, viewdir, zs[num], shapecode, texturecode)
-                    se = ((rgb - tgt_img) ** 2).sum(-1)
-                    chunk_mse = [float(se[i:i + self.B].mean()) / 3 for i in range(0, H * W, self.B)]
-                    local[num] = (float(-10 * np.log(float(np.mean(chunk_mse))) / np.log(10)),
-                                  ssim_legacy(rgb.reshape(H, W, 3).cpu().numpy(),
-                                              tgt_img.reshape(H, W, 3).cpu().numpy()))
+                    if self.device_metrics:
+                        image_metrics(rgb, tgt_img, H, W, self.B, out=met[k:k + 1])
+                    else:
+                        se = ((rgb - tgt_img) ** 2).sum(-1)
+                        chunk_mse = [float(se[i:i + self.B].mean()) / 3 for i in range(0, H * W, self.B)]
+                        local[num] = (float(-10 * np.log(float(np.mean(chunk_mse))) / np.log(10)),
+                                      ssim_legacy(rgb.reshape(H, W, 3).cpu().numpy(),
+                                                  tgt_img.reshape(H, W, 3).cpu().numpy()))
                     if save_img:
                         self.save_img([rgb.reshape(H, W, 3)], [tgt_img.reshape(H, W, 3)], self.ids[num_obj], num,
                                       opt=False)
+                if self.device_metrics:
+                    for num, (mse, ssim) in zip(mine, met.cpu().tolist()):
+                        local[num] = (float(mse_to_psnr(mse)), ssim)
                 for num, (psnr, ssim) in dp.gather_by_key(local, self.dist).items():
                     self.psnr_eval.setdefault(num_obj, []).append(psnr)
                     self.ssim_eval.setdefault(num_obj, []).append(ssim)

@@ -296,6 +296,26 @@ int cn_composite_fine_fwd(const float *d_sigma_c, const float *d_rgb_c, const fl
                           const float *d_z_f, int Nf, int R, int white_bg, float *d_out_rgb,
                           float *d_out_depth, float *d_out_acc, void *stream);
 
+/* ---- evaluation metrics of the test-time loop (additive to ABI 4) for V
+ * views at once: the PSNR argument of src/optimizer.py:117-125 and SSIM as
+ * src/optimizer.py:156 calls it (skimage structural_similarity(multichannel=
+ * True); codenerf_amd.metrics.ssim_legacy is the definition: 7x7 uniform
+ * window, sample covariance, data_range 2, image cropped by 3 per side).
+ * d_img, d_gt [V][H*W][3] contiguous, pixel = row * W + col (cn_get_rays'
+ * order).  d_out [V][2] float64 = (mse, ssim) per view, written.  mse: per
+ * chunk of `chunk` consecutive rays (ragged last chunk) the mean of
+ * (img - gt)^2 over its 3 n elements, then the plain mean of the chunk means;
+ * d_chunk_mse [V][ceil(H*W/chunk)] float64 receives the chunk means, may be
+ * NULL.  Everything after the loads is float64; two-stage sums in a fixed
+ * order through d_ws (cn_image_metrics_ws_bytes bytes; 0: arguments invalid),
+ * no atomics: deterministic, and a view's numbers do not depend on V.
+ * Returns -1 with cn_last_error() before any device call for H < 7, W < 7,
+ * V < 1, chunk < 1, H * W > CN_MAX_SAMPLES, V > 65535 or a NULL d_img, d_gt,
+ * d_out or d_ws. */
+size_t cn_image_metrics_ws_bytes(int H, int W, int V, int chunk);
+int cn_image_metrics(const float *d_img, const float *d_gt, int H, int W, int V, int chunk,
+                     double *d_out, double *d_chunk_mse, void *d_ws, void *stream);
+
 /* ---- torch.optim.AdamW step (src/trainer.py:116-120) over nseg tensors
  * (host arrays of device pointers), step = 1-based count of this update. */
 int cn_adamw_step(int nseg, float *const *p, const float *const *g, float *const *m,

@@ -3,7 +3,7 @@
   python optimize.py --saved_dir srncar --tgt_instances 1 [--splits test]
          [--num_opts 200] [--lr 1e-2] [--lr_half_interval 50] [--save_img True]
          [--optimize_pose True [--pose_lr 1e-3] [--pose_noise_deg 0] [--pose_noise_trans 0]]
-         [--n_importance N]
+         [--n_importance N] [--device_metrics True]
 
 --optimize_pose (no reference counterpart) refines every target view's camera
 pose together with the codes; the two noise flags perturb the dataset poses it
@@ -14,6 +14,11 @@ fine) renderer; left out, the JSON's ``N_importance`` decides, as in training.
 Above 0 every optimisation step (codes, and poses with --optimize_pose) runs
 through the fine pass and the evaluation views are rendered with it, with the
 deterministic fine samples u_j = (j + 0.5) / N; 0 is the coarse-only loop.
+
+--device_metrics True (default False; no reference counterpart) computes the
+evaluation views' PSNR argument and SSIM with the device kernel
+(cn_image_metrics) and reads an object's results back once after its last
+view, instead of the per-view host metrics; the outputs keep their shape.
 """
 import argparse
 import os
@@ -45,6 +50,8 @@ def build_parser():
                     help="shift each starting pose by this length times a seeded normal vector")
     ap.add_argument("--n_importance", dest="n_importance", type=int, default=None,
                     help="fine samples per ray (default: the JSON's N_importance; 0: coarse only)")
+    ap.add_argument("--device_metrics", dest="device_metrics", type=str2bool, default=False,
+                    help="evaluation PSNR / SSIM on the device, one read-back per object")
     return ap
 
 
@@ -55,7 +62,7 @@ def main():
     from codenerf_amd.optimizer import Optimizer
     tgt = [int(i) for i in args.tgt_instances]
     opt = Optimizer(args.saved_dir, int(args.gpu), tgt, args.splits, args.jsonfile, int(args.batchsize),
-                    int(args.num_opts), n_importance=args.n_importance)
+                    int(args.num_opts), n_importance=args.n_importance, device_metrics=args.device_metrics)
     if args.optimize_pose:
         noise = (args.pose_noise_deg, args.pose_noise_trans) if args.pose_noise_deg or args.pose_noise_trans else None
         opt.optimize_objs(tgt, float(args.lr), int(args.lr_half_interval), str2bool(args.save_img),
