@@ -126,29 +126,22 @@ class Optimizer:
                 gens, gts = [], []
                 for num, iid in enumerate(instance_ids):
                     tgt_img = imgs[0, iid].reshape(-1, 3).to(self.device)
+                    pp = self.pose_params[num] if self.optimize_pose else None
+                    rays_o, viewdir = pp.rays(H, W, focal) if pp else get_rays(H, W, focal, poses[0, iid])
+                    z_c = self._z_vals()
                     if self.n_fine > 0:
                         # the coarse + fine step the model was trained with,
                         # codes only; the logged loss and the image are the fine ones
-                        pp = self.pose_params[num] if self.optimize_pose else None
-                        rays_o, viewdir = pp.rays(H, W, focal) if pp else get_rays(H, W, focal, poses[0, iid])
-                        z_c = self._z_vals()
                         rand_f = torch.rand(H * W, self.n_fine, device=self.device)
                         _, losses, rgb, reg = self.step_impl.forward_backward_fine(
                             rays_o, viewdir, z_c, rand_f, tgt_img, shapecode, texturecode, 0, weight_grads=False,
-                            input_grads=self.optimize_pose)
-                        if pp:
-                            pp.backward_from_ray_grads(self.step_impl.last_ray_grads)
-                    elif self.optimize_pose:
-                        pp = self.pose_params[num]
-                        rays_o, viewdir = pp.rays(H, W, focal)
-                        losses, rgb, reg = self.step_impl.forward_backward(
-                            rays_o, viewdir, self._z_vals(), tgt_img, shapecode, texturecode, 0, weight_grads=False,
-                            input_grads=True)
-                        pp.backward_from_ray_grads(self.step_impl.last_ray_grads)
+                            input_grads=pp is not None)
                     else:
-                        rays_o, viewdir = get_rays(H, W, focal, poses[0, iid])
                         losses, rgb, reg = self.step_impl.forward_backward(
-                            rays_o, viewdir, self._z_vals(), tgt_img, shapecode, texturecode, 0, weight_grads=False)
+                            rays_o, viewdir, z_c, tgt_img, shapecode, texturecode, 0, weight_grads=False,
+                            input_grads=pp is not None)
+                    if pp:
+                        pp.backward_from_ray_grads(self.step_impl.last_ray_grads)
                     gens.append(rgb.reshape(H, W, 3))
                     gts.append(tgt_img.reshape(H, W, 3))
                 self.opts.step()

@@ -14,6 +14,14 @@ Large images (C5: 256^2 rays x 256 samples in fp32) are split into ray parts
 of whole loss chunks whose training workspace fits ``engine.ACT_BUDGET``;
 their gradients accumulate before the caller's optimiser step.
 
+One host schedule serves every step: ``forward_backward`` (coarse only) and
+``forward_backward_fine`` (coarse + fine) are the same ray-part loop
+(``_step``) over the same part function (``_part``), the coarse-only step
+being the case "no fine samples"; with fine samples the part adds sample_pdf,
+the fine forward and its loss, the optional recompute forwards and a second
+input-gradient reduction.  ``render`` and ``render_fine`` share their loop
+(``_render``) the same way.
+
 Backward schedule: the rows of a part (coarse rows, then fine rows) are cut
 into ``bwd_ranges`` row ranges; the dX chain of range i runs on the current
 stream while the weight-gradient pass of range i-1 runs on a side stream
@@ -192,76 +200,9 @@ class ImageStep:
         ``self.last_ray_grads = (d_rays_o [R,3], d_viewdirs [R,3])`` (the
         codes path then runs the backward that also stores the two input-side
         gradient planes); the return value is unchanged."""
-        eng = self.model.engine()
-        R = rays_o.shape[0]
-        N = z_vals.shape[-1]
-        z = z_vals.contiguous().to(eng.device, torch.float32)
-        losses, rgbs, regs, ray_grads = [], [], [], []
-        for k, (a, b) in enumerate(self.ray_parts(eng, R, N)):
-            zp = z if z.dim() == 1 else z[a:b]
-            l, c, r = self._coarse_part(eng, rays_o[a:b], viewdirs[a:b], zp, gt[a:b], shape_table, texture_table,
-                                        obj_idx, reg and k == 0, weight_grads, input_grads)
-            losses.append(l)
-            rgbs.append(c)
-            regs.append(r)
-            if input_grads:
-                ray_grads.append(self._part_ray_grads)
-        if input_grads:
-            self.last_ray_grads = ray_grads[0] if len(ray_grads) == 1 else (
-                torch.cat([g[0] for g in ray_grads]), torch.cat([g[1] for g in ray_grads]))
-        if len(losses) == 1:
-            return losses[0], rgbs[0], regs[0]
-        return torch.cat(losses), torch.cat(rgbs), regs[0]
-
-    def _coarse_part(self, eng, rays_o, viewdirs, z, gt, shape_table, texture_table, obj_idx, reg, weight_grads,
-                     input_grads=False):
-        params = self.model.param_list()
-        grads = self.ensure_grads(params)
-        self.ensure_grads([shape_table, texture_table])
-        self._writing_grads()
-        R = rays_o.shape[0]
-        N = z.shape[-1]
-        M = R * N
-        z_stride = 0 if z.dim() == 1 else N
-        ws = self._workspace(eng, M)
-        cap = ws["cap"]
-        Mp = eng.pad(M)
-        eng.ensure_packed(params, bwd=True)
-        s, t = shape_table.detach()[obj_idx], texture_table.detach()[obj_idx]
-        blob, zvec = eng.latent_fwd(params, s, t)
-        tm = self.timers
-        ev = tm.mark("fwd") if tm else None
-        sigma, rgb = eng.mlp_fwd(blob, M, rays_o=rays_o, rays_d=viewdirs, z=z, z_stride=z_stride, n_samples=N,
-                                 act=ws["act"], act_M=cap, act_row0=0, sigma=ws["sig"][:Mp], rgb=ws["rgb"][:Mp],
-                                 codes=not weight_grads)
-        if tm:
-            tm.done("fwd", ev, n=M)
-        dsig, drgb = ws["dsig"], ws["drgb"]
-        self._zero_pad_rows(ws, ("coarse", M), [(M, Mp)])
-        out_rgb, chunk_loss, _, _ = _eng.render_loss(sigma, rgb, z, R, N, gt, self.chunk, self.white_bg,
-                                                     dsig=dsig[:M], drgb=drgb[:M])
-        if weight_grads:
-            self._bwd_dw(eng, blob, ws, zvec, eng.table(grads), M)
-        else:
-            ev = tm.mark("bwd") if tm else None
-            eng.mlp_bwd(blob, M, dsig, drgb, ws["act"], codes=True, act_M=cap, row0=0, pose=input_grads)
-            if tm:
-                tm.done("bwd", ev, n=M)
-                ev = tm.mark("dw")
-            eng.mlp_dbias(ws["act"], M, ws["dbuf"], ws["dw"], act_M=cap)
-            if tm:
-                tm.done("dw", ev, n=M)
-            grads = ws.setdefault("scratch_grads", [torch.zeros_like(p) for p in params])
-        if input_grads:
-            # both backwards left dA of encoding_xyz and of encoding_viewdir in
-            # the workspace; the ray direction is also the view direction
-            _, _, d_ro, d_rd = eng.mlp_input_grad(ws["act"], M, rays_o=rays_o, rays_d=viewdirs, z=z,
-                                                  z_stride=z_stride, n_samples=N, act_M=cap, row0=0)
-            self._part_ray_grads = (d_ro, d_rd)
-        reg_out = torch.empty(1, dtype=torch.float32, device=eng.device)     # written by cn_latent_bwd
-        eng.latent_bwd(params, grads, s, t, zvec, ws["dbuf"], shape_table.grad[obj_idx],
-                       texture_table.grad[obj_idx], self.reg_coef if reg else 0.0, reg_out)
-        return chunk_loss, out_rgb, reg_out
+        losses, _, rgb, reg_out = self._step(rays_o, viewdirs, z_vals, None, None, gt, shape_table, texture_table,
+                                             obj_idx, reg, weight_grads, input_grads)
+        return losses, rgb, reg_out
 
     def forward_backward_fine(self, rays_o, viewdirs, z_c, rand_f, gt, shape_table, texture_table, obj_idx,
                               reg=True, z_f=None, weight_grads=True, input_grads=False):
@@ -283,143 +224,139 @@ class ImageStep:
         as in forward_backward; z_f is a constant of it (no gradient through
         sample_pdf, as in NeRF and oracle/ref_cpu.py:fine_image_step).
         Returns (coarse chunk losses, fine chunk losses, fine rgb (R,3), reg)."""
-        if self.recompute and not weight_grads:
+        return self._step(rays_o, viewdirs, z_c, rand_f, z_f, gt, shape_table, texture_table, obj_idx, reg,
+                          weight_grads, input_grads)
+
+    @staticmethod
+    def _cat(parts):
+        """A single ray part hands back its own tensor: no cat, no copy."""
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    def _step(self, rays_o, viewdirs, z_c, rand_f, z_f, gt, shape_table, texture_table, obj_idx, reg, weight_grads,
+              input_grads):
+        """The ray-part loop of both steps (rand_f None: no fine samples) ->
+        (coarse losses, fine losses or None, rgb, reg of part 0)."""
+        Nf = 0 if rand_f is None else rand_f.shape[-1]
+        if self.recompute and Nf and not weight_grads:
             raise ValueError("recompute rebuilds the weight-gradient operands: it has no codes-only form "
                              "(weight_grads=False)")
         eng = self.model.engine()
-        R = rays_o.shape[0]
-        Nc, Nf = z_c.shape[-1], rand_f.shape[-1]
         z_c = z_c.contiguous().to(eng.device, torch.float32)
-        outs, zfs, ray_grads = [], [], []
-        for k, (a, b) in enumerate(self.ray_parts(eng, R, Nc + Nf)):
-            zp = z_c if z_c.dim() == 1 else z_c[a:b]
-            outs.append(self._fine_part(eng, rays_o[a:b], viewdirs[a:b], zp, rand_f[a:b], gt[a:b], shape_table,
-                                        texture_table, obj_idx, reg and k == 0,
-                                        None if z_f is None else z_f[a:b].contiguous(), weight_grads, input_grads))
-            zfs.append(self.last_z_f)
-            if input_grads:
-                ray_grads.append(self._part_ray_grads)
+        outs = []
+        for k, (a, b) in enumerate(self.ray_parts(eng, rays_o.shape[0], z_c.shape[-1] + Nf)):
+            outs.append(self._part(eng, rays_o[a:b], viewdirs[a:b], z_c if z_c.dim() == 1 else z_c[a:b],
+                                   rand_f[a:b] if Nf else None, None if z_f is None else z_f[a:b].contiguous(),
+                                   gt[a:b], shape_table, texture_table, obj_idx, reg and k == 0, weight_grads,
+                                   input_grads))
+        loss_c, loss_f, rgb, regs, z_fs, ray_grads = zip(*outs)
         if input_grads:
-            self.last_ray_grads = ray_grads[0] if len(ray_grads) == 1 else (
-                torch.cat([g[0] for g in ray_grads]), torch.cat([g[1] for g in ray_grads]))
-        if len(outs) == 1:
-            return outs[0]
-        self.last_z_f = torch.cat(zfs)
-        return (torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs]), torch.cat([o[2] for o in outs]),
-                outs[0][3])
+            self.last_ray_grads = (self._cat([g[0] for g in ray_grads]), self._cat([g[1] for g in ray_grads]))
+        if Nf:
+            self.last_z_f = self._cat(z_fs)
+        return self._cat(loss_c), self._cat(loss_f) if Nf else None, self._cat(rgb), regs[0]
 
-    def _fine_part(self, eng, rays_o, viewdirs, z_c, rand_f, gt, shape_table, texture_table, obj_idx, reg,
-                   z_f=None, weight_grads=True, input_grads=False):
+    def _part(self, eng, rays_o, viewdirs, z_c, rand_f, z_f, gt, shape_table, texture_table, obj_idx, reg,
+              weight_grads, input_grads):
+        """One ray part of a step -> (coarse losses, fine losses, rgb, reg,
+        fine z, ray gradients): the fine entries None without fine samples
+        (rand_f None; rgb is then the coarse one), the ray gradients None
+        without input_grads."""
         params = self.model.param_list()
         grads = self.ensure_grads(params)
         self.ensure_grads([shape_table, texture_table])
         self._writing_grads()
+        tm = self.timers
         R = rays_o.shape[0]
         Nc = z_c.shape[-1]
-        Nf = rand_f.shape[-1]
+        Nf = 0 if rand_f is None else rand_f.shape[-1]
         Mc, Mf = R * Nc, R * Nf
         Mc_p = eng.pad(Mc)
-        M = Mc_p + Mf
+        M = Mc_p + Mf if Nf else Mc              # rows of the backward: coarse, its padding, fine
         Mp = eng.pad(M)
         ws = self._workspace(eng, M)
-        cap = ws["cap"]
+        cap, act = ws["cap"], ws["act"]
         sig, rgb, dsig, drgb = ws["sig"], ws["rgb"], ws["dsig"], ws["drgb"]
-        self._zero_pad_rows(ws, ("fine", Mc, Mf), [(Mc, Mc_p), (Mc_p + Mf, Mp)])
+        self._zero_pad_rows(ws, (Mc, Mf), [(Mc, Mc_p), (Mc_p + Mf, Mp)])
         eng.ensure_packed(params, bwd=True)
         s, t = shape_table.detach()[obj_idx], texture_table.detach()[obj_idx]
         blob, zvec = eng.latent_fwd(params, s, t)
-        tm = self.timers
-        ev = tm.mark("fwd") if tm else None
-        rc = self.recompute or not weight_grads      # both store only the codes forward's planes
-        zc_stride = 0 if z_c.dim() == 1 else Nc
-        sig_c, rgb_c = eng.mlp_fwd(blob, Mc, rays_o=rays_o, rays_d=viewdirs, z=z_c,
-                                   z_stride=zc_stride, n_samples=Nc, act=ws["act"], act_M=cap,
-                                   act_row0=0, sigma=sig[:Mc_p], rgb=rgb[:Mc_p], codes=rc)
-        if tm:
-            tm.done("fwd", ev, n=Mc)
-        _, loss_c, _, _ = _eng.render_loss(sig_c, rgb_c, z_c, R, Nc, gt, self.chunk, self.white_bg,
-                                           dsig=dsig[:Mc], drgb=drgb[:Mc])
-        if z_f is None:
-            z_f = _eng.sample_pdf(sig_c, z_c, R, Nc, rand_f)
-        else:
-            z_f = z_f.to(eng.device, torch.float32)
-        ev = tm.mark("fwd") if tm else None
-        sig_f, rgb_f = eng.mlp_fwd(blob, Mf, rays_o=rays_o, rays_d=viewdirs, z=z_f, z_stride=Nf, n_samples=Nf,
-                                   act=ws["act"], act_M=cap, act_row0=Mc_p, sigma=sig[Mc_p:Mp],
-                                   rgb=rgb[Mc_p:Mp], codes=rc)
-        if tm:
-            tm.done("fwd", ev, n=Mf)
-        out_f, loss_f = _eng.render_loss_fine(sig_c, rgb_c, z_c, Nc, sig_f, rgb_f, z_f, Nf, R, gt, self.chunk,
-                                              dsig[:Mc], drgb[:Mc], dsig[Mc_p:Mc_p + Mf],
-                                              drgb[Mc_p:Mc_p + Mf], self.white_bg)
-        if self.recompute:
-            # recompute A/B (SURVEY.md 7, hard part 2): the forward passes above
-            # stored only ReLU masks + sigma pre-activations; the planes the dW
-            # pass reads are produced here by a second training forward
-            if ws.get("dsig_tmp") is None or ws["dsig_tmp"].numel() < cap:   # its (discarded) outputs
-                ws["dsig_tmp"] = torch.empty(cap, dtype=torch.float32, device=eng.device)
-                ws["drgb_tmp"] = torch.empty(cap, 3, dtype=torch.float32, device=eng.device)
-            ev = tm.mark("fwd") if tm else None
-            eng.mlp_fwd(blob, Mc, rays_o=rays_o, rays_d=viewdirs, z=z_c, z_stride=0 if z_c.dim() == 1 else Nc,
-                        n_samples=Nc, act=ws["act"], act_M=cap, act_row0=0, sigma=ws["dsig_tmp"][:Mc_p],
-                        rgb=ws["drgb_tmp"][:Mc_p])
-            eng.mlp_fwd(blob, Mf, rays_o=rays_o, rays_d=viewdirs, z=z_f, z_stride=Nf, n_samples=Nf, act=ws["act"],
-                        act_M=cap, act_row0=Mc_p, sigma=ws["dsig_tmp"][Mc_p:Mp], rgb=ws["drgb_tmp"][Mc_p:Mp])
+
+        def timed(name, launch, **done):
+            # mark arms the timer of the next hot launch: nothing goes between
+            ev = tm.mark(name) if tm else None
+            out = launch()
             if tm:
-                tm.done("fwd", ev)
+                tm.done(name, ev, **done)
+            return out
+
+        # a pass = (samples, z, z stride, samples per ray, first workspace row)
+        def fwd(rows, out_sig, out_rgb, codes=False):
+            n, z, stride, N, r0 = rows
+            return eng.mlp_fwd(blob, n, rays_o=rays_o, rays_d=viewdirs, z=z, z_stride=stride, n_samples=N, act=act,
+                               act_M=cap, act_row0=r0, sigma=out_sig[r0:r0 + eng.pad(n)],
+                               rgb=out_rgb[r0:r0 + eng.pad(n)], codes=codes)
+
+        def input_grad(rows):
+            n, z, stride, N, r0 = rows
+            return eng.mlp_input_grad(act, n, rays_o=rays_o, rays_d=viewdirs, z=z, z_stride=stride, n_samples=N,
+                                      act_M=cap, row0=r0)[2:]
+
+        # codes-only and recompute (a fine-step option) both store only the codes forward's planes
+        rc = bool(self.recompute and Nf) or not weight_grads
+        coarse = (Mc, z_c, 0 if z_c.dim() == 1 else Nc, Nc, 0)
+        sig_c, rgb_c = timed("fwd", lambda: fwd(coarse, sig, rgb, rc), n=Mc)
+        out_rgb, loss_c, _, _ = _eng.render_loss(sig_c, rgb_c, z_c, R, Nc, gt, self.chunk, self.white_bg,
+                                                 dsig=dsig[:Mc], drgb=drgb[:Mc])
+        loss_f = fine = None
+        if Nf:
+            if z_f is None:
+                z_f = _eng.sample_pdf(sig_c, z_c, R, Nc, rand_f)
+            else:
+                z_f = z_f.to(eng.device, torch.float32)
+            fine = (Mf, z_f, Nf, Nf, Mc_p)
+            sig_f, rgb_f = timed("fwd", lambda: fwd(fine, sig, rgb, rc), n=Mf)
+            out_rgb, loss_f = _eng.render_loss_fine(sig_c, rgb_c, z_c, Nc, sig_f, rgb_f, z_f, Nf, R, gt, self.chunk,
+                                                    dsig[:Mc], drgb[:Mc], dsig[Mc_p:Mc_p + Mf],
+                                                    drgb[Mc_p:Mc_p + Mf], self.white_bg)
+            if self.recompute:
+                # recompute A/B (SURVEY.md 7, hard part 2): the forward passes above
+                # stored only ReLU masks + sigma pre-activations; the planes the dW
+                # pass reads are produced here by a second training forward
+                if ws.get("dsig_tmp") is None or ws["dsig_tmp"].numel() < cap:   # its (discarded) outputs
+                    ws["dsig_tmp"] = torch.empty(cap, dtype=torch.float32, device=eng.device)
+                    ws["drgb_tmp"] = torch.empty(cap, 3, dtype=torch.float32, device=eng.device)
+                timed("fwd", lambda: (fwd(coarse, ws["dsig_tmp"], ws["drgb_tmp"]),
+                                      fwd(fine, ws["dsig_tmp"], ws["drgb_tmp"])))
         if weight_grads:
             self._bwd_dw(eng, blob, ws, zvec, eng.table(grads), M)
         else:
             # one codes backward over the coarse rows, the (zero) padding and
             # the fine rows, then the bias sums the code gradients need
-            ev = tm.mark("bwd") if tm else None
-            eng.mlp_bwd(blob, M, dsig, drgb, ws["act"], codes=True, act_M=cap, row0=0, pose=input_grads)
-            if tm:
-                tm.done("bwd", ev, n=M)
-                ev = tm.mark("dw")
-            eng.mlp_dbias(ws["act"], M, ws["dbuf"], ws["dw"], act_M=cap)
-            if tm:
-                tm.done("dw", ev, n=M)
+            timed("bwd", lambda: eng.mlp_bwd(blob, M, dsig, drgb, act, codes=True, act_M=cap, row0=0,
+                                             pose=input_grads), n=M)
+            timed("dw", lambda: eng.mlp_dbias(act, M, ws["dbuf"], ws["dw"], act_M=cap), n=M)
             grads = ws.setdefault("scratch_grads", [torch.zeros_like(p) for p in params])
+        ray_grads = None
         if input_grads:
-            # the input-side gradient planes of the coarse rows and of the fine
-            # rows, each reduced over its own samples; z_f is a constant
-            _, _, dro_c, drd_c = eng.mlp_input_grad(ws["act"], Mc, rays_o=rays_o, rays_d=viewdirs, z=z_c,
-                                                    z_stride=zc_stride, n_samples=Nc, act_M=cap, row0=0)
-            _, _, dro_f, drd_f = eng.mlp_input_grad(ws["act"], Mf, rays_o=rays_o, rays_d=viewdirs, z=z_f,
-                                                    z_stride=Nf, n_samples=Nf, act_M=cap, row0=Mc_p)
-            self._part_ray_grads = (dro_c + dro_f, drd_c + drd_f)
+            # both backwards left dA of encoding_xyz and of encoding_viewdir in
+            # the workspace (the ray direction is also the view direction): the
+            # planes of the coarse rows and of the fine rows, each reduced over
+            # its own samples; z_f is a constant
+            ray_grads = input_grad(coarse)
+            if fine:
+                d_f = input_grad(fine)
+                ray_grads = (ray_grads[0] + d_f[0], ray_grads[1] + d_f[1])
         reg_out = torch.empty(1, dtype=torch.float32, device=eng.device)     # written by cn_latent_bwd
         eng.latent_bwd(params, grads, s, t, zvec, ws["dbuf"], shape_table.grad[obj_idx],
                        texture_table.grad[obj_idx], self.reg_coef if reg else 0.0, reg_out)
-        self.last_z_f = z_f
-        return loss_c, loss_f, out_f, reg_out
+        return loss_c, loss_f, out_rgb, reg_out, z_f if Nf else None, ray_grads
 
     # ------------------------------------------------------------ inference
     @torch.no_grad()
     def render(self, rays_o, viewdirs, z_vals, shape_code, texture_code):
         """Forward only (src/optimizer.py:108-124): -> rgb (R,3), depth (R,).
         No workspace; images beyond CN_MAX_SAMPLES samples go in ray parts."""
-        eng = self.model.engine()
-        params = self.model.param_list()
-        R = rays_o.shape[0]
-        N = z_vals.shape[-1]
-        z = z_vals.contiguous().to(eng.device, torch.float32)
-        eng.ensure_packed(params, bwd=False)
-        blob, _ = eng.latent_fwd(params, shape_code.reshape(-1).contiguous(), texture_code.reshape(-1).contiguous())
-        per = max(1, (eng.L.cn_max_samples() - 256) // N)
-        rgbs, depths = [], []
-        for a in range(0, R, per):
-            b = min(a + per, R)
-            zp = z if z.dim() == 1 else z[a:b]
-            sigma, rgb = eng.mlp_fwd(blob, (b - a) * N, rays_o=rays_o[a:b], rays_d=viewdirs[a:b], z=zp,
-                                     z_stride=0 if zp.dim() == 1 else N, n_samples=N)
-            c, d = _eng.composite_fwd(sigma, rgb, zp, b - a, N, self.white_bg)
-            rgbs.append(c)
-            depths.append(d)
-        if len(rgbs) == 1:
-            return rgbs[0], depths[0]
-        return torch.cat(rgbs), torch.cat(depths)
+        return self._render(rays_o, viewdirs, z_vals, 0, shape_code, texture_code)
 
     @torch.no_grad()
     def render_fine(self, rays_o, viewdirs, z_c, n_fine, shape_code, texture_code, rand_f=None, z_f=None):
@@ -430,10 +367,14 @@ class ImageStep:
         (NeRF's test-time convention; nothing is drawn).  z_f (R, n_fine)
         given: those fine samples, sample_pdf skipped.  The fine z used are
         left in ``self.last_z_f``.  No workspace; ray parts as in render."""
+        return self._render(rays_o, viewdirs, z_c, int(n_fine), shape_code, texture_code, rand_f, z_f)
+
+    def _render(self, rays_o, viewdirs, z_c, Nf, shape_code, texture_code, rand_f=None, z_f=None):
+        """The ray-part loop of both renderers (Nf 0: no fine pass)."""
         eng = self.model.engine()
         params = self.model.param_list()
         R = rays_o.shape[0]
-        Nc, Nf = z_c.shape[-1], int(n_fine)
+        Nc = z_c.shape[-1]
         z = z_c.contiguous().to(eng.device, torch.float32)
         if z_f is not None:
             z_f = z_f.contiguous().to(eng.device, torch.float32)
@@ -450,23 +391,24 @@ class ImageStep:
             zp = z if z.dim() == 1 else z[a:b]
             sig_c, rgb_c = eng.mlp_fwd(blob, n * Nc, rays_o=rays_o[a:b], rays_d=viewdirs[a:b], z=zp,
                                        z_stride=zc_stride, n_samples=Nc)
-            if z_f is not None:
-                zf = z_f[a:b]
+            if not Nf:
+                c, d = _eng.composite_fwd(sig_c, rgb_c, zp, n, Nc, self.white_bg)
             else:
-                rnd = (torch.full((n, Nf), 0.5, dtype=torch.float32, device=eng.device) if rand_f is None
-                       else rand_f[a:b])
-                zf = _eng.sample_pdf(sig_c, zp, n, Nc, rnd)
-            sig_f, rgb_f = eng.mlp_fwd(blob, n * Nf, rays_o=rays_o[a:b], rays_d=viewdirs[a:b], z=zf, z_stride=Nf,
-                                       n_samples=Nf)
-            c, d = _eng.composite_fine_fwd(sig_c, rgb_c, zp, Nc, sig_f, rgb_f, zf, Nf, n, self.white_bg)
+                if z_f is not None:
+                    zf = z_f[a:b]
+                else:
+                    rnd = (torch.full((n, Nf), 0.5, dtype=torch.float32, device=eng.device) if rand_f is None
+                           else rand_f[a:b])
+                    zf = _eng.sample_pdf(sig_c, zp, n, Nc, rnd)
+                sig_f, rgb_f = eng.mlp_fwd(blob, n * Nf, rays_o=rays_o[a:b], rays_d=viewdirs[a:b], z=zf,
+                                           z_stride=Nf, n_samples=Nf)
+                c, d = _eng.composite_fine_fwd(sig_c, rgb_c, zp, Nc, sig_f, rgb_f, zf, Nf, n, self.white_bg)
+                zfs.append(zf)
             rgbs.append(c)
             depths.append(d)
-            zfs.append(zf)
-        if len(rgbs) == 1:
-            self.last_z_f = zfs[0]
-            return rgbs[0], depths[0]
-        self.last_z_f = torch.cat(zfs)
-        return torch.cat(rgbs), torch.cat(depths)
+        if Nf:
+            self.last_z_f = self._cat(zfs)
+        return self._cat(rgbs), self._cat(depths)
 
     @torch.no_grad()
     def render_sharded(self, rays_o, viewdirs, z_vals, shape_code, texture_code, dist=None, group=None):

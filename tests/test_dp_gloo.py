@@ -255,7 +255,7 @@ def test_zero_after_fused_zero_grad_step_clears_direct_backward_writes():
     step = ImageStep(model=None)
     step.grad_listeners.append(ex.mark_dirty)
     ex.clean = True                     # as after a zero_grad AdamW step
-    step._writing_grads()               # what _coarse_part / _fine_part do before writing
+    step._writing_grads()               # what ImageStep._part does before writing
     params[0].grad.fill_(1.0)
     table.grad.fill_(2.0)
     ex.zero()
