@@ -79,6 +79,9 @@ _SIGS = {
     "cn_sample_pdf": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P]),
     "cn_render_loss_fine": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P,
                                  _P]),
+    "cn_render_loss_masked": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P]),
+    "cn_render_loss_fine_masked": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P,
+                                        _P, _P, _P, _F, _P, _P]),
     "cn_composite_fine_fwd": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "cn_image_metrics_ws_bytes": (_Z, [_I, _I, _I, _I]),
     "cn_image_metrics": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),

@@ -571,6 +571,36 @@ int cn_render_loss(const float* d_sigma, const float* d_rgb, const float* d_z, i
   return launch_check("chunk_loss_kernel");
 }
 
+// Host checks of the masked entries' extra arguments; *mk is what the kernel
+// gets (no silhouette term without a target).
+static int check_mask(const float* d_ray_weight, const float* d_acc_target, float sil_coef, float* d_out_acc,
+                      const char* who, RayMask* mk) {
+  if (!std::isfinite(sil_coef) || sil_coef < 0.f)
+    return fail(std::string(who) + ": sil_coef must be finite and not negative");
+  if (sil_coef > 0.f && !d_acc_target) return fail(std::string(who) + ": sil_coef > 0 needs d_acc_target");
+  *mk = RayMask{d_ray_weight, d_acc_target, d_acc_target ? sil_coef : 0.f, d_out_acc};
+  return 0;
+}
+
+int cn_render_loss_masked(const float* d_sigma, const float* d_rgb, const float* d_z, int z_stride, int R, int N,
+                          int white_bg, const float* d_gt, int chunk, float* d_out_rgb, float* d_ray_se,
+                          float* d_chunk_loss, float* d_dsig, float* d_drgb, const float* d_ray_weight,
+                          const float* d_acc_target, float sil_coef, float* d_out_acc, void* stream) {
+  if (!d_sigma || !d_rgb || !d_z || !d_gt || !d_out_rgb || !d_ray_se || !d_chunk_loss || !d_dsig || !d_drgb)
+    return fail("cn_render_loss_masked: NULL argument");
+  if (check_rn(R, N, "cn_render_loss_masked")) return -1;
+  if (chunk <= 0) return fail("cn_render_loss_masked: chunk must be positive");
+  if (z_stride != 0 && z_stride != N) return fail("cn_render_loss_masked: z_stride must be 0 or N");
+  RayMask mk;
+  if (check_mask(d_ray_weight, d_acc_target, sil_coef, d_out_acc, "cn_render_loss_masked", &mk)) return -1;
+  hipLaunchKernelGGL(render_loss_masked_kernel, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), d_sigma, d_rgb, d_z,
+                     z_stride, R, N, white_bg, d_gt, chunk, d_out_rgb, d_ray_se, d_dsig, d_drgb, mk);
+  if (launch_check("render_loss_masked_kernel")) return -1;
+  hipLaunchKernelGGL(chunk_loss_kernel, dim3(grid_for(R, chunk)), dim3(256), 0, S(stream), d_ray_se, R, chunk,
+                     d_chunk_loss);
+  return launch_check("chunk_loss_kernel");
+}
+
 int cn_sample_pdf(const float* d_sigma_c, const float* d_z_c, int zc_stride, int R, int Nc, const float* d_rand,
                   int Nf, float* d_z_f, void* stream) {
   if (!d_sigma_c || !d_z_c || !d_rand || !d_z_f) return fail("cn_sample_pdf: NULL argument");
@@ -599,6 +629,30 @@ int cn_render_loss_fine(const float* d_sigma_c, const float* d_rgb_c, const floa
                      d_z_c, zc_stride, Nc, d_sigma_f, d_rgb_f, d_z_f, Nf, R, white_bg, d_gt, chunk, d_out_rgb,
                      d_ray_se, d_dsig_c, d_drgb_c, d_dsig_f, d_drgb_f);
   if (launch_check("fine_render_loss_kernel")) return -1;
+  hipLaunchKernelGGL(chunk_loss_kernel, dim3(grid_for(R, chunk)), dim3(256), 0, S(stream), d_ray_se, R, chunk,
+                     d_chunk_loss);
+  return launch_check("chunk_loss_kernel");
+}
+
+int cn_render_loss_fine_masked(const float* d_sigma_c, const float* d_rgb_c, const float* d_z_c, int zc_stride, int Nc,
+                               const float* d_sigma_f, const float* d_rgb_f, const float* d_z_f, int Nf, int R,
+                               int white_bg, const float* d_gt, int chunk, float* d_out_rgb, float* d_ray_se,
+                               float* d_chunk_loss, float* d_dsig_c, float* d_drgb_c, float* d_dsig_f,
+                               float* d_drgb_f, const float* d_ray_weight, const float* d_acc_target, float sil_coef,
+                               float* d_out_acc, void* stream) {
+  if (!d_sigma_c || !d_rgb_c || !d_z_c || !d_sigma_f || !d_rgb_f || !d_z_f || !d_gt || !d_out_rgb || !d_ray_se ||
+      !d_chunk_loss || !d_dsig_c || !d_drgb_c || !d_dsig_f || !d_drgb_f)
+    return fail("cn_render_loss_fine_masked: NULL argument");
+  if (Nc <= 0 || Nf <= 0) return fail("cn_render_loss_fine_masked: Nc and Nf must be positive");
+  if (check_rn(R, Nc + Nf, "cn_render_loss_fine_masked")) return -1;
+  if (zc_stride != 0 && zc_stride != Nc) return fail("cn_render_loss_fine_masked: zc_stride must be 0 or Nc");
+  if (chunk <= 0) return fail("cn_render_loss_fine_masked: chunk must be positive");
+  RayMask mk;
+  if (check_mask(d_ray_weight, d_acc_target, sil_coef, d_out_acc, "cn_render_loss_fine_masked", &mk)) return -1;
+  hipLaunchKernelGGL(fine_render_loss_masked_kernel, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), d_sigma_c,
+                     d_rgb_c, d_z_c, zc_stride, Nc, d_sigma_f, d_rgb_f, d_z_f, Nf, R, white_bg, d_gt, chunk, d_out_rgb,
+                     d_ray_se, d_dsig_c, d_drgb_c, d_dsig_f, d_drgb_f, mk);
+  if (launch_check("fine_render_loss_masked_kernel")) return -1;
   hipLaunchKernelGGL(chunk_loss_kernel, dim3(grid_for(R, chunk)), dim3(256), 0, S(stream), d_ray_se, R, chunk,
                      d_chunk_loss);
   return launch_check("chunk_loss_kernel");

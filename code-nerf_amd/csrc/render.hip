@@ -4,6 +4,9 @@
 //   composite fwd/bwd   reference src/utils.py:34-47 and its autograd
 //   render_loss         composite + chunk-mean MSE (src/trainer.py:75) + the
 //                       composite backward, fused per ray for training
+//   render_loss_masked  the same with a weight per ray and a silhouette term
+//                       on the ray's accumulated opacity (no reference
+//                       counterpart in code)
 //
 // One wave per ray: lane l owns a contiguous run of samples, the exclusive
 // transmittance product and the reverse cumulative sum are wave scans.  Both
@@ -256,8 +259,12 @@ CN_DEV void ray_reduce(const RayState& st, float out[5]) {
 }
 
 // Backward of one ray given d rgb_final (3) and d depth, as torch autograd.
+// kAcc: g_acc, the gradient of the ray's weight sum (the silhouette term of
+// the masked losses), is added to every sample's d weight as well; without it
+// the sums are exactly the three below.
+template <bool kAcc = false>
 CN_DEV void ray_backward(const RayState& st, const float g[3], float gd, int white_bg,
-                         float* dsig, float* drgb) {
+                         float* dsig, float* drgb, float g_acc = 0.f) {
   const float gw_bg = white_bg ? -(g[0] + g[1] + g[2]) : 0.f;
   float dw[kMaxPer], wdT[kMaxPer];
   double part = 0.0;
@@ -267,6 +274,7 @@ CN_DEV void ray_backward(const RayState& st, const float g[3], float gd, int whi
       // d weights = sum_c g_c c_c  + d(wsum) + gd * z
       float v = fadd_rn(fadd_rn(fmul_rn(g[0], st.c[k][0]), fmul_rn(g[1], st.c[k][1])), fmul_rn(g[2], st.c[k][2]));
       v = fadd_rn(v, gw_bg);
+      if constexpr (kAcc) v = fadd_rn(v, g_acc);
       v = fadd_rn(v, fmul_rn(gd, st.z[k]));
       dw[k] = v;
       // grad of cumprod output T_k is dw_k * alpha_k; reversed cumsum of T_k * dT_k
@@ -325,6 +333,38 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const float* __restr
   ray_backward(st, g, gd, white_bg, dsig + (size_t)r * N, drgb + (size_t)r * N * 3);
 }
 
+// The masked variant of both loss kernels: a weight m_r >= 0 per ray (NULL:
+// 1), and with sil_coef > 0 a target a_r for the ray's accumulated opacity
+// acc_r = sum_k w_k (ray_reduce's o[4]; the fine kernel's runs over the merged
+// samples).  Per chunk of nb rays
+//   loss = sum_r [ m_r sum_c (col_rc - gt_rc)^2 + 3 sil_coef (acc_r - a_r)^2 ] / (3 nb)
+// so ray_se[r] = m_r se_r + 3 sil_coef (acc_r - a_r)^2 goes through
+// chunk_loss_kernel unchanged, d col_c = m_r (2 / (3 nb)) diff_c, and
+// d acc = sil_coef (2 / nb) (acc_r - a_r) joins every sample's d weight in
+// ray_backward.  m = 1 and sil_coef = 0 give the plain kernels' bits.  The
+// host passes sil_coef = 0 when acc_target is NULL.
+struct RayMask {
+  const float* weight;       // [R] or NULL
+  const float* acc_target;   // [R]; read only when sil_coef > 0
+  float sil_coef;
+  float* out_acc;            // [R] or NULL
+};
+
+// ray_se and the gradient of the weight sum of one masked ray; g (already
+// (2 / (3 nb)) diff) is scaled by the ray's weight in place
+CN_DEV float masked_ray_loss(const RayMask& mk, int r, int nb, float se, float acc, float g[3], float* g_acc) {
+  const float m = mk.weight ? mk.weight[r] : 1.f;
+  for (int c = 0; c < 3; ++c) g[c] = fmul_rn(m, g[c]);
+  float out = fmul_rn(m, se);
+  *g_acc = 0.f;
+  if (mk.sil_coef > 0.f) {
+    const float d = fadd_rn(acc, -mk.acc_target[r]);
+    out = fadd_rn(out, fmul_rn(fmul_rn(3.f, mk.sil_coef), fmul_rn(d, d)));
+    *g_acc = fmul_rn(fmul_rn(mk.sil_coef, 2.f / (float)nb), d);
+  }
+  return out;
+}
+
 // Training: composite, per-ray squared error, d rgb of the chunk-mean MSE
 // (chunk = `chunk` consecutive rays, src/trainer.py:69,75), composite backward.
 __global__ __launch_bounds__(256) void render_loss_kernel(const float* __restrict__ sig, const float* __restrict__ rgb,
@@ -355,6 +395,41 @@ __global__ __launch_bounds__(256) void render_loss_kernel(const float* __restric
     ray_se[r] = se;
   }
   ray_backward(st, g, 0.f, white_bg, dsig + (size_t)r * N, drgb + (size_t)r * N * 3);
+}
+
+// The same with the loss of RayMask (masked_ray_loss): the plain kernel's body
+// plus the weight, the silhouette term and the opacity output.
+__global__ __launch_bounds__(256) void render_loss_masked_kernel(const float* __restrict__ sig, const float* __restrict__ rgb,
+                             const float* __restrict__ z, int z_stride, int R, int N, int white_bg,
+                             const float* __restrict__ gt, int chunk, float* __restrict__ out_rgb,
+                             float* __restrict__ ray_se, float* __restrict__ dsig, float* __restrict__ drgb,
+                             RayMask mk) {
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= R) return;
+  RayState st;
+  ray_forward(st, sig + (size_t)r * N, rgb + (size_t)r * N * 3, z + (size_t)r * z_stride, N);
+  float o[5];
+  ray_reduce(st, o);
+  float col[3], g[3];
+  const int c0 = (r / chunk) * chunk;
+  const int nb = min(chunk, R - c0);
+  const float inv = 1.f / (float)(3 * nb);
+  float se = 0.f;
+  for (int c = 0; c < 3; ++c) {
+    col[c] = white_bg ? fadd_rn(o[c] + 1.f, -o[4]) : o[c];
+    const float diff = col[c] - gt[3 * r + c];
+    se += diff * diff;
+    // d mean(diff^2) = 2 * diff / numel
+    g[c] = fmul_rn(fmul_rn(inv, 2.f), diff);
+  }
+  float g_acc = 0.f;
+  se = masked_ray_loss(mk, r, nb, se, o[4], g, &g_acc);
+  if ((threadIdx.x & 63) == 0) {
+    for (int c = 0; c < 3; ++c) out_rgb[3 * r + c] = col[c];
+    ray_se[r] = se;
+    if (mk.out_acc) mk.out_acc[r] = o[4];
+  }
+  ray_backward<true>(st, g, 0.f, white_bg, dsig + (size_t)r * N, drgb + (size_t)r * N * 3, g_acc);
 }
 
 // chunk-mean MSE values from per-ray squared errors (one block per chunk)
@@ -538,6 +613,107 @@ __global__ __launch_bounds__(256) void fine_render_loss_kernel(
     ray_se[r] = se;
   }
   ray_backward(st, gr, 0.f, white_bg, m_dsig[wv], m_drgb[wv]);
+  wave_sync();
+  for (int p = lane; p < N; p += 64) {
+    const int src = m_src[wv][p];
+    if (src < 0) continue;
+    if (src < Nc) {
+      const size_t g = (size_t)r * Nc + src;
+      dsig_c[g] += m_dsig[wv][p];
+      for (int c = 0; c < 3; ++c) drgb_c[3 * g + c] += m_drgb[wv][3 * p + c];
+    } else {
+      const size_t g = (size_t)r * Nf + (src - Nc);
+      dsig_f[g] = m_dsig[wv][p];
+      for (int c = 0; c < 3; ++c) drgb_f[3 * g + c] = m_drgb[wv][3 * p + c];
+    }
+  }
+}
+
+// fine_render_loss_kernel with the loss of RayMask (the opacity over the merged
+// samples): the plain kernel's body plus the weight, the silhouette term and
+// the opacity output.
+__global__ __launch_bounds__(256) void fine_render_loss_masked_kernel(
+    const float* __restrict__ sig_c, const float* __restrict__ rgb_c, const float* __restrict__ zc, int zc_stride,
+    int Nc, const float* __restrict__ sig_f, const float* __restrict__ rgb_f, const float* __restrict__ zf, int Nf,
+    int R, int white_bg, const float* __restrict__ gt, int chunk, float* __restrict__ out_rgb,
+    float* __restrict__ ray_se, float* __restrict__ dsig_c, float* __restrict__ drgb_c,
+    float* __restrict__ dsig_f, float* __restrict__ drgb_f, RayMask mk) {
+  __shared__ float m_sig[4][kMaxRaySamples], m_z[4][kMaxRaySamples], m_rgb[4][kMaxRaySamples * 3];
+  __shared__ float m_dsig[4][kMaxRaySamples], m_drgb[4][kMaxRaySamples * 3];
+  __shared__ int m_src[4][kMaxRaySamples];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + wv;
+  if (r >= R) return;                       // wave-uniform; only wave-level sync below
+  const int N = Nc + Nf;
+  const float* zcr = zc + (size_t)r * zc_stride;
+  const float* zfr = zf + (size_t)r * Nf;
+  auto wave_sync = [] {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  };
+  // Every merged slot starts as "no source": with non-finite z (diverged
+  // weights) the two rank computations below need not form a permutation, and
+  // an unwritten slot must not scatter through an undefined index.
+  for (int p = lane; p < N; p += 64) m_src[wv][p] = -1;
+  // the ray's coarse and fine z staged in LDS (m_dsig is written only by the
+  // backward below): the rank searches' dependent reads then cost LDS, not
+  // global-memory, latency
+  float* zs = m_dsig[wv];
+  for (int i = lane; i < Nc; i += 64) zs[i] = zcr[i];
+  for (int j = lane; j < Nf; j += 64) zs[Nc + j] = zfr[j];
+  wave_sync();
+  // merged position = own index + number of the other list's samples before it
+  for (int i = lane; i < Nc; i += 64) {
+    const float v = zs[i];
+    int lo = 0, hi = Nf;                    // count zf < v
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (zs[Nc + mid] < v) lo = mid + 1; else hi = mid; }
+    const int p = i + lo;
+    const size_t g = (size_t)r * Nc + i;
+    m_sig[wv][p] = sig_c[g];
+    m_z[wv][p] = v;
+    m_rgb[wv][3 * p + 0] = rgb_c[3 * g + 0];
+    m_rgb[wv][3 * p + 1] = rgb_c[3 * g + 1];
+    m_rgb[wv][3 * p + 2] = rgb_c[3 * g + 2];
+    m_src[wv][p] = i;
+  }
+  for (int j = lane; j < Nf; j += 64) {
+    const float v = zs[Nc + j];
+    int lo = 0, hi = Nc;                    // count zc <= v
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (zs[mid] <= v) lo = mid + 1; else hi = mid; }
+    const int p = j + lo;
+    const size_t g = (size_t)r * Nf + j;
+    m_sig[wv][p] = sig_f[g];
+    m_z[wv][p] = v;
+    m_rgb[wv][3 * p + 0] = rgb_f[3 * g + 0];
+    m_rgb[wv][3 * p + 1] = rgb_f[3 * g + 1];
+    m_rgb[wv][3 * p + 2] = rgb_f[3 * g + 2];
+    m_src[wv][p] = Nc + j;
+  }
+  wave_sync();
+  RayState st;
+  ray_forward(st, m_sig[wv], m_rgb[wv], m_z[wv], N);
+  float o[5];
+  ray_reduce(st, o);
+  float col[3], gr[3];
+  const int c0 = (r / chunk) * chunk;
+  const int nbr = min(chunk, R - c0);
+  const float inv = 1.f / (float)(3 * nbr);
+  float se = 0.f;
+  for (int c = 0; c < 3; ++c) {
+    col[c] = white_bg ? fadd_rn(o[c] + 1.f, -o[4]) : o[c];
+    const float diff = col[c] - gt[3 * r + c];
+    se += diff * diff;
+    gr[c] = fmul_rn(fmul_rn(inv, 2.f), diff);
+  }
+  float g_acc = 0.f;
+  se = masked_ray_loss(mk, r, nbr, se, o[4], gr, &g_acc);
+  if (lane == 0) {
+    for (int c = 0; c < 3; ++c) out_rgb[3 * r + c] = col[c];
+    ray_se[r] = se;
+    if (mk.out_acc) mk.out_acc[r] = o[4];
+  }
+  ray_backward<true>(st, gr, 0.f, white_bg, m_dsig[wv], m_drgb[wv], g_acc);
   wave_sync();
   for (int p = lane; p < N; p += 64) {
     const int src = m_src[wv][p];

@@ -47,6 +47,19 @@ def load_imgs(img_dir, idxs=()):
     return torch.from_numpy(np.array(imgs))
 
 
+def load_masks(mask_dir, idxs=()):
+    """Foreground masks ``mask/*.png`` (named like ``rgb/``): nonzero in any
+    channel is foreground -> float32 {0, 1}, (n, H, W)."""
+    from PIL import Image
+    files = np.array(_sorted_files(mask_dir))[np.asarray(idxs, dtype=np.int64)]
+    masks = []
+    for f in files:
+        with Image.open(f) as im:
+            a = np.asarray(im)
+        masks.append((a.reshape(a.shape[0], a.shape[1], -1) != 0).any(-1).astype(np.float32))
+    return torch.from_numpy(np.array(masks))
+
+
 def load_intrinsic(path):
     with open(path) as f:
         lines = f.readlines()
@@ -104,6 +117,16 @@ class SRN:
         focal, H, W = load_intrinsic(intr)
         return focal, H, W, imgs, poses
 
+    def masks(self, obj_id):
+        """Foreground masks (n, H, W) of the views return_test_val_data loads,
+        from the object's ``mask/`` directory; None when it has none."""
+        base = os.path.join(self.data_dir, obj_id)
+        mask_dir = os.path.join(base, "mask")
+        if not os.path.isdir(mask_dir):
+            return None
+        n = min(self.n_test_views, len(os.listdir(os.path.join(base, "rgb"))))
+        return load_masks(mask_dir, np.arange(n))
+
 
 def collate_one(item):
     """What torch's default_collate with batch_size=1 hands the reference loop:
@@ -141,9 +164,10 @@ def look_at_srn(radius, az_deg, el_deg):
     return c2w_gl @ SRN_TO_GL          # diag is its own inverse
 
 
-def _render_object(spec, c2w_gl, H, W, focal):
+def _render_object(spec, c2w_gl, H, W, focal, return_hit=False):
     """Ray-cast an object made of axis-aligned ellipsoids (Lambert shading,
-    white background) with the reference's camera model (src/utils.py:10-19)."""
+    white background) with the reference's camera model (src/utils.py:10-19).
+    return_hit: also the (H, W) bool map of the rays that hit the object."""
     i, j = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64), indexing="xy")
     dirs = np.stack([(i - W * 0.5) / focal, -(j - H * 0.5) / focal, -np.ones_like(i)], -1)
     d = dirs @ c2w_gl[:3, :3].T
@@ -174,7 +198,8 @@ def _render_object(spec, c2w_gl, H, W, focal):
         col = np.asarray(rgb)[None, None, :] * shade[..., None]
         color = np.where(closer[..., None], col, color)
         best_t = np.where(closer, t, best_t)
-    return np.clip(color, 0, 1)
+    color = np.clip(color, 0, 1)
+    return (color, np.isfinite(best_t)) if return_hit else color
 
 
 def _object_spec(rng):
@@ -192,10 +217,11 @@ def _object_spec(rng):
 
 
 def make_synthetic_srn(root, cat="srn_cars", splits="cars_train", n_obj=4, n_views=50, H=128, W=128,
-                       focal=131.25, radius=1.3, seed=0):
+                       focal=131.25, radius=1.3, seed=0, masks=False):
     """Write an SRN-format split under ``root/cat/splits``: per object
     ``rgb/%06d.png``, ``pose/%06d.txt`` (SRN convention) and
-    ``intrinsics.txt``; views on the radius-``radius`` sphere."""
+    ``intrinsics.txt``; views on the radius-``radius`` sphere.  masks: also
+    ``mask/%06d.png`` (255 where the ray-caster hit the object, else 0)."""
     from PIL import Image
     rng = np.random.Generator(np.random.PCG64(seed))
     base = os.path.join(root, cat, splits)
@@ -203,13 +229,17 @@ def make_synthetic_srn(root, cat="srn_cars", splits="cars_train", n_obj=4, n_vie
         obj = os.path.join(base, f"synth{seed:03d}_{k:05d}")
         os.makedirs(os.path.join(obj, "rgb"), exist_ok=True)
         os.makedirs(os.path.join(obj, "pose"), exist_ok=True)
+        if masks:
+            os.makedirs(os.path.join(obj, "mask"), exist_ok=True)
         spec = _object_spec(rng)
         with open(os.path.join(obj, "intrinsics.txt"), "w") as f:
             f.write(f"{focal} {W / 2} {H / 2} 0.\n0. 0. 0.\n1.\n{H} {W}\n")
         for v in range(n_views):
             az, el = rng.uniform(-180, 180), rng.uniform(-5, 50)
             c2w_srn = look_at_srn(radius, az, el)
-            img = _render_object(spec, c2w_srn @ SRN_TO_GL, H, W, focal)
+            img, hit = _render_object(spec, c2w_srn @ SRN_TO_GL, H, W, focal, return_hit=True)
             Image.fromarray((img * 255 + 0.5).astype(np.uint8)).save(os.path.join(obj, "rgb", f"{v:06d}.png"))
+            if masks:
+                Image.fromarray(hit.astype(np.uint8) * 255).save(os.path.join(obj, "mask", f"{v:06d}.png"))
             np.savetxt(os.path.join(obj, "pose", f"{v:06d}.txt"), c2w_srn.reshape(1, 16))
     return base

@@ -251,6 +251,43 @@ def render_loss(sigma, rgb, z, R, N, gt, chunk, white_bg=True, dsig=None, drgb=N
     return out_rgb, chunk_loss, dsig, drgb
 
 
+def _mask_args(ray_weight, acc_target, sil_coef, who):
+    """Arguments of the masked loss entries: None / None / 0 is the plain loss."""
+    sil_coef = float(sil_coef)
+    if sil_coef > 0 and acc_target is None:
+        raise ValueError(f"{who}: sil_coef > 0 needs acc_target")
+    for t in (ray_weight, acc_target):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError(f"{who}: ray_weight / acc_target must be contiguous float32 tensors")
+    return sil_coef
+
+
+def render_loss_masked(sigma, rgb, z, R, N, gt, chunk, white_bg=True, dsig=None, drgb=None, ray_weight=None,
+                       acc_target=None, sil_coef=0.0):
+    """render_loss with per-ray weights m (R,) and the silhouette term: per
+    chunk of nb rays, sum_r [m_r se_r + 3 sil_coef (acc_r - acc_target_r)^2]
+    / (3 nb), acc = the ray's weight sum.  ray_weight None: m = 1; sil_coef 0
+    or acc_target None: no silhouette term.
+    -> (rgb, chunk losses, dsig, drgb, acc (R,))."""
+    L = _lib.lib()
+    dev = sigma.device
+    sil_coef = _mask_args(ray_weight, acc_target, sil_coef, "render_loss_masked")
+    z_stride = 0 if z.numel() == N else N
+    out_rgb = torch.empty(R, 3, dtype=torch.float32, device=dev)
+    ray_se = torch.empty(R, dtype=torch.float32, device=dev)
+    acc = torch.empty(R, dtype=torch.float32, device=dev)
+    chunk_loss = torch.empty((R + chunk - 1) // chunk, dtype=torch.float32, device=dev)
+    if dsig is None:
+        dsig = torch.empty(R * N, dtype=torch.float32, device=dev)
+    if drgb is None:
+        drgb = torch.empty(R * N, 3, dtype=torch.float32, device=dev)
+    check(L.cn_render_loss_masked(ptr(sigma), ptr(rgb), ptr(z), z_stride, R, N, int(white_bg), ptr(gt), chunk,
+                                  ptr(out_rgb), ptr(ray_se), ptr(chunk_loss), ptr(dsig), ptr(drgb),
+                                  ptr(ray_weight), ptr(acc_target), sil_coef, ptr(acc), _dev_stream(sigma)),
+          "cn_render_loss_masked")
+    return out_rgb, chunk_loss, dsig, drgb, acc
+
+
 def sample_pdf(sigma_c, z_c, R, Nc, rand):
     """Fine z (R, Nf) from the coarse densities; rand (R, Nf) in [0, 1)."""
     L = _lib.lib()
@@ -277,6 +314,27 @@ def render_loss_fine(sigma_c, rgb_c, z_c, Nc, sigma_f, rgb_f, z_f, Nf, R, gt, ch
                                 ptr(chunk_loss), ptr(dsig_c), ptr(drgb_c), ptr(dsig_f), ptr(drgb_f),
                                 _dev_stream(sigma_c)), "cn_render_loss_fine")
     return out_rgb, chunk_loss
+
+
+def render_loss_fine_masked(sigma_c, rgb_c, z_c, Nc, sigma_f, rgb_f, z_f, Nf, R, gt, chunk, dsig_c, drgb_c,
+                            dsig_f, drgb_f, white_bg=True, ray_weight=None, acc_target=None, sil_coef=0.0):
+    """render_loss_fine with the weights and the silhouette term of
+    render_loss_masked (acc over the merged samples).
+    -> (rgb (R,3), chunk losses, acc (R,))."""
+    L = _lib.lib()
+    dev = sigma_c.device
+    sil_coef = _mask_args(ray_weight, acc_target, sil_coef, "render_loss_fine_masked")
+    zc_stride = 0 if z_c.numel() == Nc else Nc
+    out_rgb = torch.empty(R, 3, dtype=torch.float32, device=dev)
+    ray_se = torch.empty(R, dtype=torch.float32, device=dev)
+    acc = torch.empty(R, dtype=torch.float32, device=dev)
+    chunk_loss = torch.empty((R + chunk - 1) // chunk, dtype=torch.float32, device=dev)
+    check(L.cn_render_loss_fine_masked(ptr(sigma_c), ptr(rgb_c), ptr(z_c), zc_stride, Nc, ptr(sigma_f), ptr(rgb_f),
+                                       ptr(z_f), Nf, R, int(white_bg), ptr(gt), chunk, ptr(out_rgb), ptr(ray_se),
+                                       ptr(chunk_loss), ptr(dsig_c), ptr(drgb_c), ptr(dsig_f), ptr(drgb_f),
+                                       ptr(ray_weight), ptr(acc_target), sil_coef, ptr(acc),
+                                       _dev_stream(sigma_c)), "cn_render_loss_fine_masked")
+    return out_rgb, chunk_loss, acc
 
 
 def composite_fine_fwd(sigma_c, rgb_c, z_c, Nc, sigma_f, rgb_f, z_f, Nf, R, white_bg=True, acc=False):

@@ -32,6 +32,16 @@ view's chunk-mean MSE and that SSIM with ``metrics.image_metrics`` on the
 device and reads all of an object's views back at once, instead of one host
 synchronisation per chunk, two image copies and a numpy SSIM per view; the
 dictionaries and ``codes.pth`` keep their shape and keys.
+``mask`` (no reference counterpart in code; the paper's real-image experiments
+mask the loss) weights the target views' loss per ray and, with ``sil_coef``,
+supervises the accumulated opacity: ``"white"`` takes a pixel as foreground
+when any channel of the target is below 1.0 (SRN's white background),
+``"files"`` reads the object's ``mask/`` directory.  Target views only:
+ray_weight = fg + bg_weight (1 - fg), acc_target = fg, through
+``ImageStep.forward_backward[_fine](ray_weight=, acc_target=, sil_coef=)``.
+``psnr_opt`` then logs -10 log10 of the MASKED loss's value (weighted MSE +
+silhouette term over all pixels of the chunk), not a PSNR of the image; the
+evaluation views are scored unmasked.  ``mask=None`` is exactly the loop above.
 """
 import json
 import os
@@ -54,7 +64,7 @@ from .utils import get_rays, image_float_to_uint8
 class Optimizer:
     def __init__(self, saved_dir, gpu=0, instance_ids=(), splits="test", jsonfile="srncar.json",
                  batch_size=2048, num_opts=200, hpams=None, exp_root="exps", dist=None, n_importance=None,
-                 device_metrics=False):
+                 device_metrics=False, mask=None, bg_weight=0.0, sil_coef=0.0):
         self.hpams = hpams if hpams is not None else load_hpams(jsonfile)
         # fine samples per ray (the JSON's N_importance, as Trainer reads it;
         # n_importance overrides it); 0: the reference's coarse-only loop
@@ -62,6 +72,12 @@ class Optimizer:
         # evaluation PSNR / SSIM from the device kernel (metrics.image_metrics),
         # one read-back per object; off: the host loop below, as the reference
         self.device_metrics = bool(device_metrics)
+        if mask not in (None, "white", "files"):
+            raise ValueError(f"mask must be None, 'white' or 'files', got {mask!r}")
+        # per-ray weights / opacity targets of the target views (module docstring)
+        self.mask, self.bg_weight, self.sil_coef = mask, float(bg_weight), float(sil_coef)
+        if self.bg_weight < 0 or self.sil_coef < 0:
+            raise ValueError("bg_weight and sil_coef must not be negative")
         self.device = torch.device("cuda", int(gpu))
         torch.cuda.set_device(self.device)
         self.exp_root = exp_root
@@ -110,6 +126,7 @@ class Optimizer:
         for num_obj in range(n):
             focal, H, W, imgs, poses, obj_idx = collate_one(self.dataset[num_obj])
             H, W = int(H), int(W)
+            fgs = self._foreground(num_obj, imgs, instance_ids)
             self.nopts = 0
             shapecode = self.mean_shape.to(self.device).clone().detach().requires_grad_()
             texturecode = self.mean_texture.to(self.device).clone().detach().requires_grad_()
@@ -129,17 +146,21 @@ class Optimizer:
                     pp = self.pose_params[num] if self.optimize_pose else None
                     rays_o, viewdir = pp.rays(H, W, focal) if pp else get_rays(H, W, focal, poses[0, iid])
                     z_c = self._z_vals()
+                    kw = {}
+                    if fgs is not None:
+                        fg = fgs[num]
+                        kw = dict(ray_weight=fg + self.bg_weight * (1 - fg), acc_target=fg, sil_coef=self.sil_coef)
                     if self.n_fine > 0:
                         # the coarse + fine step the model was trained with,
                         # codes only; the logged loss and the image are the fine ones
                         rand_f = torch.rand(H * W, self.n_fine, device=self.device)
                         _, losses, rgb, reg = self.step_impl.forward_backward_fine(
                             rays_o, viewdir, z_c, rand_f, tgt_img, shapecode, texturecode, 0, weight_grads=False,
-                            input_grads=pp is not None)
+                            input_grads=pp is not None, **kw)
                     else:
                         losses, rgb, reg = self.step_impl.forward_backward(
                             rays_o, viewdir, z_c, tgt_img, shapecode, texturecode, 0, weight_grads=False,
-                            input_grads=pp is not None)
+                            input_grads=pp is not None, **kw)
                     if pp:
                         pp.backward_from_ray_grads(self.step_impl.last_ray_grads)
                     gens.append(rgb.reshape(H, W, 3))
@@ -197,6 +218,24 @@ class Optimizer:
                 self.pose_rot_err[num_obj] = [e[0] for e in errs]
                 self.pose_trans_err[num_obj] = [e[1] for e in errs]
             self.save_opts(num_obj)
+
+    def _foreground(self, num_obj, imgs, instance_ids):
+        """Foreground {0, 1} of every target view, (H*W,) each on the device,
+        in instance_ids order; None without a mask."""
+        if self.mask is None:
+            return None
+        if self.mask == "files":
+            m = self.dataset.masks(self.ids[num_obj])
+            if m is None:
+                raise FileNotFoundError(f"mask='files': object {self.ids[num_obj]} has no mask/ directory under "
+                                        f"{self.dataset.data_dir}")
+            if tuple(m.shape[1:]) != tuple(imgs.shape[2:4]):
+                raise ValueError(f"mask='files': masks of {self.ids[num_obj]} are {tuple(m.shape[1:])}, the images "
+                                 f"{tuple(imgs.shape[2:4])}")
+            fg = [m[iid] for iid in instance_ids]
+        else:
+            fg = [(imgs[0, iid] < 1.0).any(-1).float() for iid in instance_ids]
+        return [f.reshape(-1).to(self.device) for f in fg]
 
     def _start_pose(self, c2w, pose_noise, view):
         """PoseParam of one target view: the dataset pose, perturbed by

@@ -57,6 +57,7 @@ class ImageStep:
         self.recompute = False
         self.last_ray_grads = None               # forward_backward[_fine](input_grads=True)
         self.last_z_f = None                     # fine z of the last forward_backward_fine / render_fine
+        self.last_acc = None                     # per-ray opacity of the last masked loss (ray_weight / acc_target)
         self._ws = {}                            # device -> grow-only workspace
         self._side = {}                          # device -> side stream
         # called whenever a step starts writing .grad (dp.GradExchange's
@@ -190,7 +191,8 @@ class ImageStep:
 
     # ------------------------------------------------------------ steps
     def forward_backward(self, rays_o, viewdirs, z_vals, gt, shape_table, texture_table, obj_idx,
-                         reg=True, weight_grads=True, input_grads=False):
+                         reg=True, weight_grads=True, input_grads=False, ray_weight=None, acc_target=None,
+                         sil_coef=0.0):
         """One image: returns (chunk losses [ceil(R/chunk)], rendered rgb [R,3],
         reg loss [1]).  Gradients are accumulated into .grad.  weight_grads
         False (codes-only optimisation, src/optimizer.py): the weight-gradient
@@ -199,13 +201,23 @@ class ImageStep:
         of the summed chunk losses with respect to every ray is left in
         ``self.last_ray_grads = (d_rays_o [R,3], d_viewdirs [R,3])`` (the
         codes path then runs the backward that also stores the two input-side
-        gradient planes); the return value is unchanged."""
+        gradient planes); the return value is unchanged.
+        ray_weight (R,), acc_target (R,), sil_coef (no reference counterpart in
+        code; the paper's real-image experiments mask the loss): any of them
+        given, the loss of a chunk of nb rays is sum_r [m_r se_r + 3 sil_coef
+        (acc_r - acc_target_r)^2] / (3 nb) with m = ray_weight (None: 1) and
+        acc_r the ray's accumulated opacity (engine.render_loss_masked), on
+        every path alike; nothing after the loss kernel changes.  The opacity
+        of every ray is then left in ``self.last_acc``.  With the defaults the
+        step is the plain one, call for call."""
         losses, _, rgb, reg_out = self._step(rays_o, viewdirs, z_vals, None, None, gt, shape_table, texture_table,
-                                             obj_idx, reg, weight_grads, input_grads)
+                                             obj_idx, reg, weight_grads, input_grads,
+                                             self._mask(ray_weight, acc_target, sil_coef, rays_o))
         return losses, rgb, reg_out
 
     def forward_backward_fine(self, rays_o, viewdirs, z_c, rand_f, gt, shape_table, texture_table, obj_idx,
-                              reg=True, z_f=None, weight_grads=True, input_grads=False):
+                              reg=True, z_f=None, weight_grads=True, input_grads=False, ray_weight=None,
+                              acc_target=None, sil_coef=0.0):
         """Coarse + fine image step (the BASELINE configs' "64 + 64"; no
         reference counterpart -- NeRF hierarchical sampling through the one
         CodeNeRF MLP, oracle/ref_cpu.py:fine_image_step).  Loss = coarse
@@ -223,9 +235,28 @@ class ImageStep:
         losses with respect to every ray is left in ``self.last_ray_grads``
         as in forward_backward; z_f is a constant of it (no gradient through
         sample_pdf, as in NeRF and oracle/ref_cpu.py:fine_image_step).
+        ray_weight, acc_target, sil_coef: as in forward_backward, applied to
+        the coarse and to the fine loss alike (the fine opacity runs over the
+        merged samples); ``self.last_acc`` is the fine loss's.
         Returns (coarse chunk losses, fine chunk losses, fine rgb (R,3), reg)."""
         return self._step(rays_o, viewdirs, z_c, rand_f, z_f, gt, shape_table, texture_table, obj_idx, reg,
-                          weight_grads, input_grads)
+                          weight_grads, input_grads, self._mask(ray_weight, acc_target, sil_coef, rays_o))
+
+    @staticmethod
+    def _mask(ray_weight, acc_target, sil_coef, rays_o):
+        """(ray_weight, acc_target, sil_coef) of a masked step on the rays'
+        device, or None for the plain loss."""
+        if ray_weight is None and acc_target is None and not sil_coef:
+            return None
+        R = rays_o.shape[0]
+        out = []
+        for name, t in (("ray_weight", ray_weight), ("acc_target", acc_target)):
+            if t is not None:
+                t = t.reshape(-1).to(rays_o.device, torch.float32).contiguous()
+                if t.numel() != R:
+                    raise ValueError(f"{name} must hold one value per ray ({R}), got {t.numel()}")
+            out.append(t)
+        return out[0], out[1], float(sil_coef)
 
     @staticmethod
     def _cat(parts):
@@ -233,7 +264,7 @@ class ImageStep:
         return parts[0] if len(parts) == 1 else torch.cat(parts)
 
     def _step(self, rays_o, viewdirs, z_c, rand_f, z_f, gt, shape_table, texture_table, obj_idx, reg, weight_grads,
-              input_grads):
+              input_grads, mask=None):
         """The ray-part loop of both steps (rand_f None: no fine samples) ->
         (coarse losses, fine losses or None, rgb, reg of part 0)."""
         Nf = 0 if rand_f is None else rand_f.shape[-1]
@@ -247,8 +278,11 @@ class ImageStep:
             outs.append(self._part(eng, rays_o[a:b], viewdirs[a:b], z_c if z_c.dim() == 1 else z_c[a:b],
                                    rand_f[a:b] if Nf else None, None if z_f is None else z_f[a:b].contiguous(),
                                    gt[a:b], shape_table, texture_table, obj_idx, reg and k == 0, weight_grads,
-                                   input_grads))
-        loss_c, loss_f, rgb, regs, z_fs, ray_grads = zip(*outs)
+                                   input_grads,
+                                   mask and tuple(None if t is None else t[a:b] for t in mask[:2]) + mask[2:]))
+        loss_c, loss_f, rgb, regs, z_fs, ray_grads, accs = zip(*outs)
+        if mask:
+            self.last_acc = self._cat(accs)
         if input_grads:
             self.last_ray_grads = (self._cat([g[0] for g in ray_grads]), self._cat([g[1] for g in ray_grads]))
         if Nf:
@@ -256,11 +290,12 @@ class ImageStep:
         return self._cat(loss_c), self._cat(loss_f) if Nf else None, self._cat(rgb), regs[0]
 
     def _part(self, eng, rays_o, viewdirs, z_c, rand_f, z_f, gt, shape_table, texture_table, obj_idx, reg,
-              weight_grads, input_grads):
+              weight_grads, input_grads, mask=None):
         """One ray part of a step -> (coarse losses, fine losses, rgb, reg,
-        fine z, ray gradients): the fine entries None without fine samples
-        (rand_f None; rgb is then the coarse one), the ray gradients None
-        without input_grads."""
+        fine z, ray gradients, opacity): the fine entries None without fine
+        samples (rand_f None; rgb is then the coarse one), the ray gradients
+        None without input_grads, the opacity None without mask = (ray
+        weights, opacity targets, silhouette coefficient) of the part's rays."""
         params = self.model.param_list()
         grads = self.ensure_grads(params)
         self.ensure_grads([shape_table, texture_table])
@@ -305,8 +340,15 @@ class ImageStep:
         rc = bool(self.recompute and Nf) or not weight_grads
         coarse = (Mc, z_c, 0 if z_c.dim() == 1 else Nc, Nc, 0)
         sig_c, rgb_c = timed("fwd", lambda: fwd(coarse, sig, rgb, rc), n=Mc)
-        out_rgb, loss_c, _, _ = _eng.render_loss(sig_c, rgb_c, z_c, R, Nc, gt, self.chunk, self.white_bg,
-                                                 dsig=dsig[:Mc], drgb=drgb[:Mc])
+        acc = None
+        if mask:
+            mw, ma, lam = mask
+            out_rgb, loss_c, _, _, acc = _eng.render_loss_masked(sig_c, rgb_c, z_c, R, Nc, gt, self.chunk,
+                                                                 self.white_bg, dsig=dsig[:Mc], drgb=drgb[:Mc],
+                                                                 ray_weight=mw, acc_target=ma, sil_coef=lam)
+        else:
+            out_rgb, loss_c, _, _ = _eng.render_loss(sig_c, rgb_c, z_c, R, Nc, gt, self.chunk, self.white_bg,
+                                                     dsig=dsig[:Mc], drgb=drgb[:Mc])
         loss_f = fine = None
         if Nf:
             if z_f is None:
@@ -315,9 +357,15 @@ class ImageStep:
                 z_f = z_f.to(eng.device, torch.float32)
             fine = (Mf, z_f, Nf, Nf, Mc_p)
             sig_f, rgb_f = timed("fwd", lambda: fwd(fine, sig, rgb, rc), n=Mf)
-            out_rgb, loss_f = _eng.render_loss_fine(sig_c, rgb_c, z_c, Nc, sig_f, rgb_f, z_f, Nf, R, gt, self.chunk,
-                                                    dsig[:Mc], drgb[:Mc], dsig[Mc_p:Mc_p + Mf],
-                                                    drgb[Mc_p:Mc_p + Mf], self.white_bg)
+            if mask:
+                out_rgb, loss_f, acc = _eng.render_loss_fine_masked(
+                    sig_c, rgb_c, z_c, Nc, sig_f, rgb_f, z_f, Nf, R, gt, self.chunk, dsig[:Mc], drgb[:Mc],
+                    dsig[Mc_p:Mc_p + Mf], drgb[Mc_p:Mc_p + Mf], self.white_bg, ray_weight=mw, acc_target=ma,
+                    sil_coef=lam)
+            else:
+                out_rgb, loss_f = _eng.render_loss_fine(sig_c, rgb_c, z_c, Nc, sig_f, rgb_f, z_f, Nf, R, gt,
+                                                        self.chunk, dsig[:Mc], drgb[:Mc], dsig[Mc_p:Mc_p + Mf],
+                                                        drgb[Mc_p:Mc_p + Mf], self.white_bg)
             if self.recompute:
                 # recompute A/B (hard part 2): the forward passes above
                 # stored only ReLU masks + sigma pre-activations; the planes the dW
@@ -349,7 +397,7 @@ class ImageStep:
         reg_out = torch.empty(1, dtype=torch.float32, device=eng.device)     # written by cn_latent_bwd
         eng.latent_bwd(params, grads, s, t, zvec, ws["dbuf"], shape_table.grad[obj_idx],
                        texture_table.grad[obj_idx], self.reg_coef if reg else 0.0, reg_out)
-        return loss_c, loss_f, out_rgb, reg_out, z_f if Nf else None, ray_grads
+        return loss_c, loss_f, out_rgb, reg_out, z_f if Nf else None, ray_grads, acc
 
     # ------------------------------------------------------------ inference
     @torch.no_grad()

@@ -286,6 +286,34 @@ int cn_render_loss_fine(const float *d_sigma_c, const float *d_rgb_c, const floa
                         float *d_dsig_c, float *d_drgb_c, float *d_dsig_f, float *d_drgb_f,
                         void *stream);
 
+/* ---- masked image loss (no reference counterpart in code; the paper's
+ * real-image experiments mask the loss; additive to ABI 4).  The two loss
+ * entries above with a weight m_r >= 0 per ray and a silhouette term on the
+ * ray's accumulated opacity acc_r = sum_k w_k (over the merged samples in the
+ * fine entry): per chunk of nb rays
+ *   loss = sum_r [ m_r sum_c (col_rc - gt_rc)^2 + 3 sil_coef (acc_r - a_r)^2 ] / (3 nb)
+ * (the denominator is the chunk's size, not sum m: defined for a chunk
+ * without foreground), d_ray_se[r] holding the bracket.  Arguments as the
+ * plain entry's, then: d_ray_weight [R] (NULL: m = 1), d_acc_target [R] = a
+ * (NULL: no silhouette term), sil_coef >= 0 (0: no silhouette term),
+ * d_out_acc [R] = acc, may be NULL.  m = 1 and no silhouette term give the
+ * plain entry's results bit for bit.  Returns -1 with cn_last_error() before
+ * any launch for the plain entry's refusals, a z stride other than 0 or the
+ * coarse sample count, sil_coef negative or not finite, and sil_coef > 0
+ * with a NULL d_acc_target. */
+int cn_render_loss_masked(const float *d_sigma, const float *d_rgb, const float *d_z, int z_stride,
+                          int R, int N, int white_bg, const float *d_gt, int chunk,
+                          float *d_out_rgb, float *d_ray_se, float *d_chunk_loss, float *d_dsigma,
+                          float *d_drgb, const float *d_ray_weight, const float *d_acc_target,
+                          float sil_coef, float *d_out_acc, void *stream);
+int cn_render_loss_fine_masked(const float *d_sigma_c, const float *d_rgb_c, const float *d_z_c,
+                               int zc_stride, int Nc, const float *d_sigma_f, const float *d_rgb_f,
+                               const float *d_z_f, int Nf, int R, int white_bg, const float *d_gt,
+                               int chunk, float *d_out_rgb, float *d_ray_se, float *d_chunk_loss,
+                               float *d_dsig_c, float *d_drgb_c, float *d_dsig_f, float *d_drgb_f,
+                               const float *d_ray_weight, const float *d_acc_target, float sil_coef,
+                               float *d_out_acc, void *stream);
+
 /* forward half of cn_render_loss_fine (test-time rendering; additive to ABI
  * 4): the same merge of each ray's coarse and fine samples (a coarse sample
  * precedes a fine one at equal z; Nc + Nf <= 256, zc_stride 0 or Nc), so

@@ -4,6 +4,7 @@
          [--num_opts 200] [--lr 1e-2] [--lr_half_interval 50] [--save_img True]
          [--optimize_pose True [--pose_lr 1e-3] [--pose_noise_deg 0] [--pose_noise_trans 0]]
          [--n_importance N] [--device_metrics True]
+         [--mask {none,white,files} [--bg_weight 0] [--sil_coef 0]]
 
 --optimize_pose (no reference counterpart) refines every target view's camera
 pose together with the codes; the two noise flags perturb the dataset poses it
@@ -19,6 +20,16 @@ deterministic fine samples u_j = (j + 0.5) / N; 0 is the coarse-only loop.
 evaluation views' PSNR argument and SSIM with the device kernel
 (cn_image_metrics) and reads an object's results back once after its last
 view, instead of the per-view host metrics; the outputs keep their shape.
+
+--mask (default none; no reference counterpart in code -- the paper's
+real-image experiments mask the loss) weights the image loss of the target
+views per ray: ``white`` takes every pixel with a channel below 1.0 as
+foreground (SRN's white background), ``files`` reads the object's ``mask/``
+directory (PNGs named like ``rgb/``, nonzero = foreground).  A foreground ray
+weighs 1, a background ray --bg_weight (default 0: background, occluder and
+clutter pixels pull neither the codes nor the pose).  --sil_coef (default 0)
+adds coef x mean (accumulated opacity - mask)^2 over the rays, the silhouette
+term.  The evaluation views are scored unmasked; ``none`` is the plain loop.
 """
 import argparse
 import os
@@ -52,6 +63,13 @@ def build_parser():
                     help="fine samples per ray (default: the JSON's N_importance; 0: coarse only)")
     ap.add_argument("--device_metrics", dest="device_metrics", type=str2bool, default=False,
                     help="evaluation PSNR / SSIM on the device, one read-back per object")
+    ap.add_argument("--mask", dest="mask", choices=["none", "white", "files"], default="none",
+                    help="per-ray weights of the target views' loss: foreground from the white "
+                         "background or from the object's mask/ directory")
+    ap.add_argument("--bg_weight", dest="bg_weight", type=float, default=0.0,
+                    help="weight of a background ray under --mask (foreground rays weigh 1)")
+    ap.add_argument("--sil_coef", dest="sil_coef", type=float, default=0.0,
+                    help="coefficient of the silhouette term (accumulated opacity against the mask)")
     return ap
 
 
@@ -62,7 +80,9 @@ def main():
     from codenerf_amd.optimizer import Optimizer
     tgt = [int(i) for i in args.tgt_instances]
     opt = Optimizer(args.saved_dir, int(args.gpu), tgt, args.splits, args.jsonfile, int(args.batchsize),
-                    int(args.num_opts), n_importance=args.n_importance, device_metrics=args.device_metrics)
+                    int(args.num_opts), n_importance=args.n_importance, device_metrics=args.device_metrics,
+                    mask=None if args.mask == "none" else args.mask, bg_weight=args.bg_weight,
+                    sil_coef=args.sil_coef)
     if args.optimize_pose:
         noise = (args.pose_noise_deg, args.pose_noise_trans) if args.pose_noise_deg or args.pose_noise_trans else None
         opt.optimize_objs(tgt, float(args.lr), int(args.lr_half_interval), str2bool(args.save_img),
