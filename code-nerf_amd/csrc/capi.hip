@@ -15,6 +15,7 @@
 #include "optim.hip"
 #include "render.hip"
 #include "metrics.hip"
+#include "sparse.hip"
 #include "inputgrad.hip"
 #include "probe.hip"
 
@@ -670,6 +671,67 @@ int cn_composite_fine_fwd(const float* d_sigma_c, const float* d_rgb_c, const fl
                      d_z_c, zc_stride, Nc, d_sigma_f, d_rgb_f, d_z_f, Nf, R, white_bg, d_out_rgb, d_out_depth,
                      d_out_acc);
   return launch_check("composite_fine_fwd_kernel");
+}
+
+// Host checks shared by the occupancy-grid entries (no device call).
+static int check_grid(int G, const char* who) {
+  if (G < 32 || G > 256 || G % 32) return fail(std::string(who) + ": G must be a multiple of 32 in [32, 256]");
+  return 0;
+}
+static int check_sparse_rn(int R, int N, const char* who) {
+  if (R < 1) return fail(std::string(who) + ": R must be at least 1");
+  if (N < 1 || N > 32 * kKeepWords) return fail(std::string(who) + ": N must be in [1, 256]");
+  if ((long long)R * N > CN_MAX_SAMPLES)
+    return fail(std::string(who) + ": R * N exceeds CN_MAX_SAMPLES; split the rays into parts");
+  return 0;
+}
+
+int cn_occupancy_build(const float* d_sigma, int G, float tau, int dilate, uint32_t* d_bits, void* stream) {
+  if (!d_sigma || !d_bits) return fail("cn_occupancy_build: NULL argument");
+  if (check_grid(G, "cn_occupancy_build")) return -1;
+  if (dilate < 0 || dilate > 4) return fail("cn_occupancy_build: dilate must be in [0, 4]");
+  if (std::isnan(tau)) return fail("cn_occupancy_build: tau is NaN");
+  const long words = (long)G * G * (G / 32);
+  hipLaunchKernelGGL(occupancy_build_kernel, dim3(grid_for(words, 256)), dim3(256), 0, S(stream), d_sigma, G, tau,
+                     dilate, d_bits);
+  return launch_check("occupancy_build_kernel");
+}
+
+int cn_sparse_mark(const float* d_rays_o, const float* d_rays_d, const float* d_z, int z_stride, int R, int N,
+                   const uint32_t* d_bits, int G, float lo_x, float lo_y, float lo_z, float inv_cell, int keep_last,
+                   uint32_t* d_keep, int* d_count, void* stream) {
+  if (!d_rays_o || !d_rays_d || !d_z || !d_bits || !d_keep || !d_count) return fail("cn_sparse_mark: NULL argument");
+  if (check_sparse_rn(R, N, "cn_sparse_mark")) return -1;
+  if (z_stride != 0 && z_stride != N) return fail("cn_sparse_mark: z_stride must be 0 or N");
+  if (check_grid(G, "cn_sparse_mark")) return -1;
+  if (!std::isfinite(inv_cell) || !(inv_cell > 0.f)) return fail("cn_sparse_mark: inv_cell must be finite and positive");
+  if (!std::isfinite(lo_x) || !std::isfinite(lo_y) || !std::isfinite(lo_z))
+    return fail("cn_sparse_mark: lo must be finite");
+  const SparseGrid g{d_bits, G, {lo_x, lo_y, lo_z}, inv_cell};
+  hipLaunchKernelGGL(sparse_mark_kernel, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), d_rays_o, d_rays_d, d_z,
+                     z_stride, R, N, g, keep_last ? 1 : 0, d_keep, d_count);
+  return launch_check("sparse_mark_kernel");
+}
+
+int cn_sparse_gather(const float* d_rays_o, const float* d_rays_d, const float* d_z, int z_stride, int R, int N,
+                     const uint32_t* d_keep, const int* d_offset, float* d_xyz, float* d_viewdir, void* stream) {
+  if (!d_rays_o || !d_rays_d || !d_z || !d_keep || !d_offset || !d_xyz || !d_viewdir)
+    return fail("cn_sparse_gather: NULL argument");
+  if (check_sparse_rn(R, N, "cn_sparse_gather")) return -1;
+  if (z_stride != 0 && z_stride != N) return fail("cn_sparse_gather: z_stride must be 0 or N");
+  hipLaunchKernelGGL(sparse_gather_kernel, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), d_rays_o, d_rays_d, d_z,
+                     z_stride, R, N, d_keep, d_offset, d_xyz, d_viewdir);
+  return launch_check("sparse_gather_kernel");
+}
+
+int cn_sparse_scatter(const uint32_t* d_keep, const int* d_offset, int R, int N, const float* d_sigma_k,
+                      const float* d_rgb_k, float* d_sigma, float* d_rgb, void* stream) {
+  if (!d_keep || !d_offset || !d_sigma_k || !d_rgb_k || !d_sigma || !d_rgb)
+    return fail("cn_sparse_scatter: NULL argument");
+  if (check_sparse_rn(R, N, "cn_sparse_scatter")) return -1;
+  hipLaunchKernelGGL(sparse_scatter_kernel, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), d_keep, d_offset, R, N,
+                     d_sigma_k, d_rgb_k, d_sigma, d_rgb);
+  return launch_check("sparse_scatter_kernel");
 }
 
 // Argument check shared by the size query and the call (no device call).

@@ -352,6 +352,60 @@ def composite_fine_fwd(sigma_c, rgb_c, z_c, Nc, sigma_f, rgb_f, z_f, Nf, R, whit
     return (out_rgb, depth, out_acc) if acc else (out_rgb, depth)
 
 
+def occupancy_build(sigma, G, tau, dilate=0):
+    """Grid bits (G^3 / 32 words, int32 storage) from the densities at the G^3
+    cell centres: sigma >= tau (NaN occupied), dilated by `dilate` cells
+    (cn_occupancy_build)."""
+    L = _lib.lib()
+    if sigma.numel() != G ** 3 or sigma.dtype != torch.float32 or not sigma.is_contiguous():
+        raise ValueError(f"occupancy_build: sigma must hold G^3 = {G ** 3} contiguous float32 values")
+    bits = torch.empty(G ** 3 // 32, dtype=torch.int32, device=sigma.device)
+    check(L.cn_occupancy_build(ptr(sigma), int(G), float(tau), int(dilate), ptr(bits), _dev_stream(sigma)),
+          "cn_occupancy_build")
+    return bits
+
+
+def sparse_mark(rays_o, rays_d, z, R, N, bits, G, lo, inv_cell, keep_last=True):
+    """Which samples fall in a set cell of the grid (cn_sparse_mark)
+    -> (keep (R, 8) int32 bit words, count (R,) int32)."""
+    L = _lib.lib()
+    if bits.numel() != G ** 3 // 32:
+        raise ValueError(f"sparse_mark: a grid of {G}^3 cells has {G ** 3 // 32} words, got {bits.numel()}")
+    z_stride = 0 if z.numel() == N else N
+    keep = torch.empty(R, 8, dtype=torch.int32, device=rays_o.device)
+    count = torch.empty(R, dtype=torch.int32, device=rays_o.device)
+    check(L.cn_sparse_mark(ptr(rays_o), ptr(rays_d), ptr(z), z_stride, R, N, ptr(bits), int(G), float(lo[0]),
+                           float(lo[1]), float(lo[2]), float(inv_cell), int(bool(keep_last)), ptr(keep), ptr(count),
+                           _dev_stream(rays_o)), "cn_sparse_mark")
+    return keep, count
+
+
+def sparse_gather(rays_o, rays_d, z, R, N, keep, offset, Mk):
+    """Points and view directions of the Mk kept samples, ray-major
+    (cn_sparse_gather); offset (R,) int32 = the exclusive prefix sum of
+    sparse_mark's counts, Mk their sum.  -> (xyz (Mk, 3), viewdir (Mk, 3))."""
+    L = _lib.lib()
+    z_stride = 0 if z.numel() == N else N
+    xyz = torch.empty(Mk, 3, dtype=torch.float32, device=rays_o.device)
+    vd = torch.empty(Mk, 3, dtype=torch.float32, device=rays_o.device)
+    check(L.cn_sparse_gather(ptr(rays_o), ptr(rays_d), ptr(z), z_stride, R, N, ptr(keep), ptr(offset), ptr(xyz),
+                             ptr(vd), _dev_stream(rays_o)), "cn_sparse_gather")
+    return xyz, vd
+
+
+def sparse_scatter(keep, offset, R, N, sigma_k, rgb_k, sigma=None, rgb=None):
+    """Dense sigma (R*N,) and rgb (R*N, 3) from the compact rows: 0 at every
+    sample that is not kept (cn_sparse_scatter)."""
+    L = _lib.lib()
+    if sigma is None:
+        sigma = torch.empty(R * N, dtype=torch.float32, device=keep.device)
+    if rgb is None:
+        rgb = torch.empty(R * N, 3, dtype=torch.float32, device=keep.device)
+    check(L.cn_sparse_scatter(ptr(keep), ptr(offset), R, N, ptr(sigma_k), ptr(rgb_k), ptr(sigma), ptr(rgb),
+                              _dev_stream(keep)), "cn_sparse_scatter")
+    return sigma, rgb
+
+
 def get_rays_dev(H, W, focal, focal_is_f64, c2w):
     L = _lib.lib()
     dev = c2w.device

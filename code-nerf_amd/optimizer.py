@@ -42,6 +42,19 @@ ray_weight = fg + bg_weight (1 - fg), acc_target = fg, through
 ``psnr_opt`` then logs -10 log10 of the MASKED loss's value (weighted MSE +
 silhouette term over all pixels of the chunk), not a PSNR of the image; the
 evaluation views are scored unmasked.  ``mask=None`` is exactly the loop above.
+``sparse_eval=True`` (no reference counterpart) renders the evaluation views
+through an occupancy grid (``occupancy.OccupancyGrid``): once an
+object's codes are final, one grid of ``occ_grid``^3 cells over the box
+[-occ_bound, occ_bound]^3 (None: (far - near) / 2, the radius the sample range
+covers around the origin) is built from its optimised shape code (density >=
+``occ_tau``, dilated by ``occ_dilate`` cells), and every evaluation view, on
+either metrics path, evaluates the MLP only at the samples in its set cells.
+Samples outside the box are culled whatever the grid holds, and the default
+box holds the sample range of the central ray only: a model with density
+beyond it needs a larger ``occ_bound`` (DESIGN.md 8.4 has the figures).
+The optimisation steps are untouched: the codes move, so no grid is valid for
+them.  The grid's set share and the mean kept share of the samples are left in
+``occ_fraction`` / ``occ_kept`` per object; ``codes.pth`` keeps its keys.
 """
 import json
 import os
@@ -54,6 +67,7 @@ from . import dp
 from .data import SRN, collate_one
 from .metrics import image_metrics, psnr as mse_to_psnr, ssim_legacy
 from .model import CodeNeRF
+from .occupancy import OccupancyGrid
 from .optim import FusedAdamW
 from .pose import PoseParam, perturb_pose
 from .render import ImageStep
@@ -61,10 +75,15 @@ from .trainer import load_hpams
 from .utils import get_rays, image_float_to_uint8
 
 
+# Defaults of the evaluation grid (sparse_eval): DESIGN.md 8.4 has the sweep they come from.
+OCC_GRID, OCC_TAU, OCC_DILATE = 128, 1e-1, 2
+
+
 class Optimizer:
     def __init__(self, saved_dir, gpu=0, instance_ids=(), splits="test", jsonfile="srncar.json",
                  batch_size=2048, num_opts=200, hpams=None, exp_root="exps", dist=None, n_importance=None,
-                 device_metrics=False, mask=None, bg_weight=0.0, sil_coef=0.0):
+                 device_metrics=False, mask=None, bg_weight=0.0, sil_coef=0.0, sparse_eval=False, occ_grid=OCC_GRID,
+                 occ_tau=OCC_TAU, occ_dilate=OCC_DILATE, occ_bound=None):
         self.hpams = hpams if hpams is not None else load_hpams(jsonfile)
         # fine samples per ray (the JSON's N_importance, as Trainer reads it;
         # n_importance overrides it); 0: the reference's coarse-only loop
@@ -78,6 +97,19 @@ class Optimizer:
         self.mask, self.bg_weight, self.sil_coef = mask, float(bg_weight), float(sil_coef)
         if self.bg_weight < 0 or self.sil_coef < 0:
             raise ValueError("bg_weight and sil_coef must not be negative")
+        # evaluation views through an occupancy grid of the optimised shape code (module docstring)
+        self.sparse_eval = bool(sparse_eval)
+        self.occ_grid, self.occ_tau, self.occ_dilate = int(occ_grid), float(occ_tau), int(occ_dilate)
+        self.occ_bound = None if occ_bound is None else float(occ_bound)
+        if not self.occ_tau >= 0:
+            raise ValueError("occ_tau must not be negative")
+        if not 0 <= self.occ_dilate <= 4:
+            raise ValueError("occ_dilate must be in [0, 4]")
+        if self.occ_grid % 32 or not 32 <= self.occ_grid <= 256:
+            raise ValueError("occ_grid must be a multiple of 32 in [32, 256]")
+        if self.occ_bound is not None and not self.occ_bound > 0:
+            raise ValueError("occ_bound must be positive")
+        self.occ_fraction, self.occ_kept = {}, {}
         self.device = torch.device("cuda", int(gpu))
         torch.cuda.set_device(self.device)
         self.exp_root = exp_root
@@ -180,6 +212,12 @@ class Optimizer:
                 zs = {num: self._z_vals() for num in views}
                 local = {}
                 mine = dp.shard(views, self.dist)
+                grid, kept = None, []
+                if self.sparse_eval and mine:
+                    bound = self.occ_bound if self.occ_bound is not None else \
+                        (self.hpams["far"] - self.hpams["near"]) / 2
+                    grid = OccupancyGrid.build(self.model, shapecode, G=self.occ_grid, bound=bound, tau=self.occ_tau,
+                                               dilate=self.occ_dilate)
                 if self.device_metrics:
                     # (mse, ssim) of every local view, read back once after the last
                     met = torch.empty(len(mine), 2, dtype=torch.float64, device=self.device)
@@ -189,9 +227,13 @@ class Optimizer:
                     if self.n_fine > 0:
                         # deterministic fine samples: the split changes no result
                         rgb, _ = self.step_impl.render_fine(rays_o, viewdir, zs[num], self.n_fine, shapecode,
-                                                            texturecode)
+                                                            texturecode, occupancy=grid)
                     else:
-                        rgb, _ = self.step_impl.render(rays_o, viewdir, zs[num], shapecode, texturecode)
+                        rgb, _ = self.step_impl.render(rays_o, viewdir, zs[num], shapecode, texturecode,
+                                                       occupancy=grid)
+                    if grid is not None:
+                        kc, kf, tot = self.step_impl.last_sparse
+                        kept.append((kc + kf) / tot)
                     if self.device_metrics:
                         image_metrics(rgb, tgt_img, H, W, self.B, out=met[k:k + 1])
                     else:
@@ -206,6 +248,11 @@ class Optimizer:
                 if self.device_metrics:
                     for num, (mse, ssim) in zip(mine, met.cpu().tolist()):
                         local[num] = (float(mse_to_psnr(mse)), ssim)
+                if grid is not None:
+                    self.occ_fraction[num_obj] = grid.fraction()
+                    self.occ_kept[num_obj] = float(np.mean(kept))
+                    print(f"object {num_obj}: occupancy grid {self.occ_grid}^3, {self.occ_fraction[num_obj]:.4f} of "
+                          f"the cells set, {self.occ_kept[num_obj]:.4f} of the samples kept over {len(kept)} views")
                 for num, (psnr, ssim) in dp.gather_by_key(local, self.dist).items():
                     self.psnr_eval.setdefault(num_obj, []).append(psnr)
                     self.ssim_eval.setdefault(num_obj, []).append(ssim)

@@ -58,6 +58,7 @@ class ImageStep:
         self.last_ray_grads = None               # forward_backward[_fine](input_grads=True)
         self.last_z_f = None                     # fine z of the last forward_backward_fine / render_fine
         self.last_acc = None                     # per-ray opacity of the last masked loss (ray_weight / acc_target)
+        self.last_sparse = None                  # (kept coarse, kept fine, total) samples of the last render through a grid
         self._ws = {}                            # device -> grow-only workspace
         self._side = {}                          # device -> side stream
         # called whenever a step starts writing .grad (dp.GradExchange's
@@ -401,23 +402,53 @@ class ImageStep:
 
     # ------------------------------------------------------------ inference
     @torch.no_grad()
-    def render(self, rays_o, viewdirs, z_vals, shape_code, texture_code):
+    def render(self, rays_o, viewdirs, z_vals, shape_code, texture_code, occupancy=None):
         """Forward only (src/optimizer.py:108-124): -> rgb (R,3), depth (R,).
-        No workspace; images beyond CN_MAX_SAMPLES samples go in ray parts."""
-        return self._render(rays_o, viewdirs, z_vals, 0, shape_code, texture_code)
+        No workspace; images beyond CN_MAX_SAMPLES samples go in ray parts.
+        occupancy (an ``occupancy.OccupancyGrid`` built for this shape code; no
+        reference counterpart): the MLP is evaluated only at the samples in
+        set cells of the grid and at the last sample of every ray; the density
+        and colour of every other sample are 0 and nothing else changes
+        (DESIGN.md 8.4).  One host synchronisation per pass reads the kept
+        count back.  ``self.last_sparse = (kept coarse, kept fine, total)``
+        samples of the call.  None: the dense render, call for call."""
+        return self._render(rays_o, viewdirs, z_vals, 0, shape_code, texture_code, occupancy=occupancy)
 
     @torch.no_grad()
-    def render_fine(self, rays_o, viewdirs, z_c, n_fine, shape_code, texture_code, rand_f=None, z_f=None):
+    def render_fine(self, rays_o, viewdirs, z_c, n_fine, shape_code, texture_code, rand_f=None, z_f=None,
+                    occupancy=None):
         """Forward only through the coarse + fine renderer the fine step
         trains (no reference counterpart): coarse pass -> sample_pdf -> fine
         pass -> composite over the merged samples -> rgb (R,3), depth (R,).
         rand_f None: the deterministic samples u_j = (j + 0.5) / n_fine
         (NeRF's test-time convention; nothing is drawn).  z_f (R, n_fine)
         given: those fine samples, sample_pdf skipped.  The fine z used are
-        left in ``self.last_z_f``.  No workspace; ray parts as in render."""
-        return self._render(rays_o, viewdirs, z_c, int(n_fine), shape_code, texture_code, rand_f, z_f)
+        left in ``self.last_z_f``.  No workspace; ray parts as in render.
+        occupancy: as in render, for the coarse pass (last sample kept) and
+        the fine pass (grid cells only).  The last coarse sample is also the
+        last of the merged ray, because sample_pdf's bins are midpoints of the
+        coarse z; a caller-supplied z_f beyond it gives that guarantee up
+        (a ray whose last merged sample is culled is not opaque)."""
+        return self._render(rays_o, viewdirs, z_c, int(n_fine), shape_code, texture_code, rand_f, z_f, occupancy)
 
-    def _render(self, rays_o, viewdirs, z_c, Nf, shape_code, texture_code, rand_f=None, z_f=None):
+    def _sparse_fwd(self, eng, blob, rays_o, viewdirs, z, n, N, occ, keep_last):
+        """The MLP pass of one ray part through the grid: mark -> prefix sum ->
+        gather -> MLP on the kept points -> scatter.  -> (sigma (n N,), rgb
+        (n N, 3), kept samples); reading the kept count back synchronises."""
+        keep, count = _eng.sparse_mark(rays_o, viewdirs, z, n, N, occ.bits, occ.G, occ.lo, occ.inv_cell, keep_last)
+        incl = torch.cumsum(count, 0, dtype=torch.int32)
+        Mk = int(incl[-1])                       # cn_mlp_fwd takes its sample count on the host
+        if Mk == 0:
+            dev = rays_o.device
+            return (torch.zeros(n * N, dtype=torch.float32, device=dev),
+                    torch.zeros(n * N, 3, dtype=torch.float32, device=dev), 0)
+        off = incl - count
+        xyz, vd = _eng.sparse_gather(rays_o, viewdirs, z, n, N, keep, off, Mk)
+        sig_k, rgb_k = eng.mlp_fwd(blob, Mk, xyz=xyz, viewdir=vd)
+        sig, rgb = _eng.sparse_scatter(keep, off, n, N, sig_k, rgb_k)
+        return sig, rgb, Mk
+
+    def _render(self, rays_o, viewdirs, z_c, Nf, shape_code, texture_code, rand_f=None, z_f=None, occupancy=None):
         """The ray-part loop of both renderers (Nf 0: no fine pass)."""
         eng = self.model.engine()
         params = self.model.param_list()
@@ -433,12 +464,21 @@ class ImageStep:
         per = max(1, (eng.L.cn_max_samples() - 256) // max(Nc, Nf))
         zc_stride = 0 if z.dim() == 1 else Nc
         rgbs, depths, zfs = [], [], []
+        occ = occupancy
+        kept_c = kept_f = 0
+        if occ is not None:
+            rays_o = rays_o.contiguous().to(eng.device, torch.float32)
+            viewdirs = viewdirs.contiguous().to(eng.device, torch.float32)
         for a in range(0, R, per):
             b = min(a + per, R)
             n = b - a
             zp = z if z.dim() == 1 else z[a:b]
-            sig_c, rgb_c = eng.mlp_fwd(blob, n * Nc, rays_o=rays_o[a:b], rays_d=viewdirs[a:b], z=zp,
-                                       z_stride=zc_stride, n_samples=Nc)
+            if occ is not None:
+                sig_c, rgb_c, k = self._sparse_fwd(eng, blob, rays_o[a:b], viewdirs[a:b], zp, n, Nc, occ, True)
+                kept_c += k
+            else:
+                sig_c, rgb_c = eng.mlp_fwd(blob, n * Nc, rays_o=rays_o[a:b], rays_d=viewdirs[a:b], z=zp,
+                                           z_stride=zc_stride, n_samples=Nc)
             if not Nf:
                 c, d = _eng.composite_fwd(sig_c, rgb_c, zp, n, Nc, self.white_bg)
             else:
@@ -448,14 +488,20 @@ class ImageStep:
                     rnd = (torch.full((n, Nf), 0.5, dtype=torch.float32, device=eng.device) if rand_f is None
                            else rand_f[a:b])
                     zf = _eng.sample_pdf(sig_c, zp, n, Nc, rnd)
-                sig_f, rgb_f = eng.mlp_fwd(blob, n * Nf, rays_o=rays_o[a:b], rays_d=viewdirs[a:b], z=zf,
-                                           z_stride=Nf, n_samples=Nf)
+                if occ is not None:
+                    sig_f, rgb_f, k = self._sparse_fwd(eng, blob, rays_o[a:b], viewdirs[a:b], zf, n, Nf, occ, False)
+                    kept_f += k
+                else:
+                    sig_f, rgb_f = eng.mlp_fwd(blob, n * Nf, rays_o=rays_o[a:b], rays_d=viewdirs[a:b], z=zf,
+                                               z_stride=Nf, n_samples=Nf)
                 c, d = _eng.composite_fine_fwd(sig_c, rgb_c, zp, Nc, sig_f, rgb_f, zf, Nf, n, self.white_bg)
                 zfs.append(zf)
             rgbs.append(c)
             depths.append(d)
         if Nf:
             self.last_z_f = self._cat(zfs)
+        if occ is not None:
+            self.last_sparse = (kept_c, kept_f, R * (Nc + Nf))
         return self._cat(rgbs), self._cat(depths)
 
     @torch.no_grad()

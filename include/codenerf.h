@@ -324,6 +324,49 @@ int cn_composite_fine_fwd(const float *d_sigma_c, const float *d_rgb_c, const fl
                           const float *d_z_f, int Nf, int R, int white_bg, float *d_out_rgb,
                           float *d_out_depth, float *d_out_acc, void *stream);
 
+/* ---- rendering through an occupancy grid (additive to ABI 4; no reference
+ * counterpart).  The grid is G^3 cells (G a multiple of 32 in [32, 256]) over
+ * the box [lo, lo + G / inv_cell)^3, one bit per cell: cell c = (ix G + iy) G
+ * + iz is bit c & 31 of word c >> 5 of d_bits [G^3 / 32].  A sample s of ray r
+ * is KEPT when its point, in float32 with separately rounded operations as
+ * cn_mlp_fwd's ray mode forms it,
+ *   x_a = o_a + d_a z,  t_a = (x_a - lo_a) inv_cell,  0 <= t_a < G (NaN: no),
+ * lies in a set cell i_a = floor(t_a); with keep_last the last sample of every
+ * ray is kept as well.  The sparse render of a view is the dense render with
+ * the density and colour of every sample that is not kept replaced by 0: mark
+ * -> exclusive prefix sum of d_count (the caller's) -> gather -> cn_mlp_fwd on
+ * the explicit points -> scatter -> the unchanged compositing entries.  No
+ * atomics: every output is deterministic.
+ * Each entry returns -1 with cn_last_error() naming it, before any device
+ * call, for a NULL pointer, R < 1, N outside [1, 256], R * N >
+ * CN_MAX_SAMPLES, z_stride other than 0 or N, G not a multiple of 32 in
+ * [32, 256], dilate outside [0, 4], tau NaN, inv_cell not finite and positive
+ * or a lo that is not finite.
+ *
+ * cn_occupancy_build: d_sigma [G^3] holds the density at the cell centres in
+ * the cell order above; a cell is occupied when sigma >= tau (NaN: occupied),
+ * and its bit is the OR over the cells within Chebyshev distance `dilate`,
+ * clamped at the box faces.  Every word of d_bits is written. */
+int cn_occupancy_build(const float *d_sigma, int G, float tau, int dilate, uint32_t *d_bits,
+                       void *stream);
+/* d_keep [R][8]: bit s & 31 of word s >> 5 says sample s is kept (bits >= N and
+ * unused words 0); d_count [R]: kept samples of the ray.  Both written. */
+int cn_sparse_mark(const float *d_rays_o, const float *d_rays_d, const float *d_z, int z_stride,
+                   int R, int N, const uint32_t *d_bits, int G, float lo_x, float lo_y, float lo_z,
+                   float inv_cell, int keep_last, uint32_t *d_keep, int *d_count, void *stream);
+/* d_offset [R]: the exclusive prefix sum of d_count.  Kept sample s of ray r
+ * goes to row d_offset[r] + (kept samples of r below s) of d_xyz / d_viewdir
+ * [Mk][3] (ray-major, samples ascending; Mk = sum of d_count): the point x
+ * above and the ray direction.  Rows >= Mk are not written. */
+int cn_sparse_gather(const float *d_rays_o, const float *d_rays_d, const float *d_z, int z_stride,
+                     int R, int N, const uint32_t *d_keep, const int *d_offset, float *d_xyz,
+                     float *d_viewdir, void *stream);
+/* the inverse: d_sigma [R*N] and d_rgb [R*N][3] get the compact row at kept
+ * samples and 0 elsewhere; every element is written. */
+int cn_sparse_scatter(const uint32_t *d_keep, const int *d_offset, int R, int N,
+                      const float *d_sigma_k, const float *d_rgb_k, float *d_sigma, float *d_rgb,
+                      void *stream);
+
 /* ---- evaluation metrics of the test-time loop (additive to ABI 4) for V
  * views at once: the PSNR argument of src/optimizer.py:117-125 and SSIM as
  * src/optimizer.py:156 calls it (skimage structural_similarity(multichannel=

@@ -5,6 +5,7 @@
          [--optimize_pose True [--pose_lr 1e-3] [--pose_noise_deg 0] [--pose_noise_trans 0]]
          [--n_importance N] [--device_metrics True]
          [--mask {none,white,files} [--bg_weight 0] [--sil_coef 0]]
+         [--sparse_eval True [--occ_grid 128] [--occ_tau 1e-1] [--occ_dilate 2] [--occ_bound B]]
 
 --optimize_pose (no reference counterpart) refines every target view's camera
 pose together with the codes; the two noise flags perturb the dataset poses it
@@ -30,6 +31,13 @@ weighs 1, a background ray --bg_weight (default 0: background, occluder and
 clutter pixels pull neither the codes nor the pose).  --sil_coef (default 0)
 adds coef x mean (accumulated opacity - mask)^2 over the rays, the silhouette
 term.  The evaluation views are scored unmasked; ``none`` is the plain loop.
+
+--sparse_eval True (default False; no reference counterpart) renders the
+evaluation views through an occupancy grid built once per object from its
+optimised shape code: --occ_grid cells per axis over [-B, B]^3 (--occ_bound,
+default (far - near) / 2), a cell set when the density at its centre reaches
+--occ_tau, dilated by --occ_dilate cells.  Samples in empty cells are not
+evaluated (density and colour 0); the optimisation steps are untouched.
 """
 import argparse
 import os
@@ -70,6 +78,15 @@ def build_parser():
                     help="weight of a background ray under --mask (foreground rays weigh 1)")
     ap.add_argument("--sil_coef", dest="sil_coef", type=float, default=0.0,
                     help="coefficient of the silhouette term (accumulated opacity against the mask)")
+    ap.add_argument("--sparse_eval", dest="sparse_eval", type=str2bool, default=False,
+                    help="render the evaluation views through an occupancy grid of the optimised shape code")
+    ap.add_argument("--occ_grid", dest="occ_grid", type=int, default=None, help="grid cells per axis")
+    ap.add_argument("--occ_tau", dest="occ_tau", type=float, default=None,
+                    help="a cell is occupied when the density at its centre reaches this")
+    ap.add_argument("--occ_dilate", dest="occ_dilate", type=int, default=None,
+                    help="dilate the occupied cells by this many cells (0 to 4)")
+    ap.add_argument("--occ_bound", dest="occ_bound", type=float, default=None,
+                    help="half edge of the grid's box around the origin (default (far - near) / 2)")
     return ap
 
 
@@ -82,7 +99,9 @@ def main():
     opt = Optimizer(args.saved_dir, int(args.gpu), tgt, args.splits, args.jsonfile, int(args.batchsize),
                     int(args.num_opts), n_importance=args.n_importance, device_metrics=args.device_metrics,
                     mask=None if args.mask == "none" else args.mask, bg_weight=args.bg_weight,
-                    sil_coef=args.sil_coef)
+                    sil_coef=args.sil_coef, sparse_eval=args.sparse_eval, occ_bound=args.occ_bound,
+                    **{k: getattr(args, k) for k in ("occ_grid", "occ_tau", "occ_dilate")
+                       if getattr(args, k) is not None})
     if args.optimize_pose:
         noise = (args.pose_noise_deg, args.pose_noise_trans) if args.pose_noise_deg or args.pose_noise_trans else None
         opt.optimize_objs(tgt, float(args.lr), int(args.lr_half_interval), str2bool(args.save_img),
