@@ -16,6 +16,7 @@
 #include "render.hip"
 #include "metrics.hip"
 #include "sparse.hip"
+#include "mesh.hip"
 #include "inputgrad.hip"
 #include "probe.hip"
 
@@ -732,6 +733,42 @@ int cn_sparse_scatter(const uint32_t* d_keep, const int* d_offset, int R, int N,
   hipLaunchKernelGGL(sparse_scatter_kernel, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), d_keep, d_offset, R, N,
                      d_sigma_k, d_rgb_k, d_sigma, d_rgb);
   return launch_check("sparse_scatter_kernel");
+}
+
+// Host checks shared by the two iso-surface entries (no device call).
+static int check_mesh(const char* who, int nx, int ny, int nz, float iso) {
+  const int n[3] = {nx, ny, nz};
+  for (int a = 0; a < 3; ++a)
+    if (n[a] < 2 || n[a] > 1024) return fail(std::string(who) + ": every dimension must be in [2, 1024]");
+  if ((long long)nx * ny * nz > (1ll << 27)) return fail(std::string(who) + ": nx * ny * nz exceeds 2^27 lattice points");
+  if (std::isnan(iso)) return fail(std::string(who) + ": iso is NaN");
+  return 0;
+}
+
+int cn_mesh_count(const float* d_field, int nx, int ny, int nz, float iso, uint8_t* d_vflags, int* d_vcount,
+                  int* d_tcount, void* stream) {
+  if (!d_field || !d_vflags || !d_vcount || !d_tcount) return fail("cn_mesh_count: NULL argument");
+  if (check_mesh("cn_mesh_count", nx, ny, nz, iso)) return -1;
+  const long P = (long)nx * ny * nz;
+  hipLaunchKernelGGL(mesh_count_kernel, dim3(grid_for(P, 256)), dim3(256), 0, S(stream), d_field,
+                     MeshDims{nx, ny, nz}, iso, d_vflags, d_vcount, d_tcount);
+  return launch_check("mesh_count_kernel");
+}
+
+int cn_mesh_emit(const float* d_field, int nx, int ny, int nz, float iso, float lo_x, float lo_y, float lo_z,
+                 float s_x, float s_y, float s_z, const uint8_t* d_vflags, const int* d_voff, const int* d_toff,
+                 float* d_vert, int* d_tri, void* stream) {
+  if (!d_field || !d_vflags || !d_voff || !d_toff || !d_vert || !d_tri) return fail("cn_mesh_emit: NULL argument");
+  if (check_mesh("cn_mesh_emit", nx, ny, nz, iso)) return -1;
+  for (float s : {s_x, s_y, s_z})
+    if (!std::isfinite(s) || !(s > 0.f)) return fail("cn_mesh_emit: spacing must be finite and positive");
+  if (!std::isfinite(lo_x) || !std::isfinite(lo_y) || !std::isfinite(lo_z))
+    return fail("cn_mesh_emit: lo must be finite");
+  const long P = (long)nx * ny * nz;
+  hipLaunchKernelGGL(mesh_emit_kernel, dim3(grid_for(P, 256)), dim3(256), 0, S(stream), d_field,
+                     MeshDims{nx, ny, nz}, iso, lo_x, lo_y, lo_z, s_x, s_y, s_z, d_vflags, d_voff, d_toff, d_vert,
+                     d_tri);
+  return launch_check("mesh_emit_kernel");
 }
 
 // Argument check shared by the size query and the call (no device call).

@@ -406,6 +406,49 @@ def sparse_scatter(keep, offset, R, N, sigma_k, rgb_k, sigma=None, rgb=None):
     return sigma, rgb
 
 
+def _mesh_field(field, dims, who):
+    nx, ny, nz = (int(n) for n in dims)
+    if field.dtype != torch.float32 or not field.is_contiguous() or field.numel() != nx * ny * nz:
+        raise ValueError(f"{who}: field must hold nx * ny * nz = {nx * ny * nz} contiguous float32 values")
+    return nx, ny, nz
+
+
+def mesh_count(field, dims, iso):
+    """Crossing edges and triangles per lattice point (cn_mesh_count)
+    -> (vflags uint8 [P], vcount int32 [P], tcount int32 [P])."""
+    L = _lib.lib()
+    nx, ny, nz = _mesh_field(field, dims, "mesh_count")
+    P = nx * ny * nz
+    vflags = torch.empty(P, dtype=torch.uint8, device=field.device)
+    vcount = torch.empty(P, dtype=torch.int32, device=field.device)
+    tcount = torch.empty(P, dtype=torch.int32, device=field.device)
+    check(L.cn_mesh_count(ptr(field), nx, ny, nz, float(iso), ptr(vflags), ptr(vcount), ptr(tcount),
+                          _dev_stream(field)), "cn_mesh_count")
+    return vflags, vcount, tcount
+
+
+def mesh_emit(field, dims, iso, lo, spacing, vflags, voff, toff, Nv, Nt, vert=None, tri=None):
+    """Vertices and triangles of the iso-surface (cn_mesh_emit); voff / toff
+    (P,) int32 = the exclusive prefix sums of mesh_count's counts, Nv / Nt their
+    sums.  -> (vert (Nv, 3) float32, tri (Nt, 3) int32); rows past Nv / Nt of
+    larger buffers handed in are left alone."""
+    L = _lib.lib()
+    nx, ny, nz = _mesh_field(field, dims, "mesh_emit")
+    for t, dt in ((vflags, torch.uint8), (voff, torch.int32), (toff, torch.int32)):
+        if t.dtype != dt or not t.is_contiguous() or t.numel() != nx * ny * nz:
+            raise ValueError("mesh_emit: vflags (uint8), voff and toff (int32) must hold one contiguous value per point")
+    if vert is None:
+        vert = torch.empty(Nv, 3, dtype=torch.float32, device=field.device)
+    if tri is None:
+        tri = torch.empty(Nt, 3, dtype=torch.int32, device=field.device)
+    if vert.numel() < 3 * Nv or tri.numel() < 3 * Nt:
+        raise ValueError("mesh_emit: vert / tri hold fewer than Nv / Nt rows")
+    check(L.cn_mesh_emit(ptr(field), nx, ny, nz, float(iso), float(lo[0]), float(lo[1]), float(lo[2]),
+                         float(spacing[0]), float(spacing[1]), float(spacing[2]), ptr(vflags), ptr(voff), ptr(toff),
+                         ptr(vert), ptr(tri), _dev_stream(field)), "cn_mesh_emit")
+    return vert, tri
+
+
 def get_rays_dev(H, W, focal, focal_is_f64, c2w):
     L = _lib.lib()
     dev = c2w.device

@@ -19,6 +19,23 @@ from . import engine as _eng
 CHUNK = 1 << 20          # points per MLP launch of build()
 
 
+def eval_density(eng, blob, total, points):
+    """Density (total,) of the engine's plan at the points ``points(a, b)`` ->
+    float32 (b - a, 3) of rows [a, b): explicit points, at most CHUNK per
+    launch, view direction (0, 0, 1) (it does not enter the density).  Shared
+    by OccupancyGrid.build and mesh.extract_mesh."""
+    dev = eng.device
+    sigma = torch.empty(total, dtype=torch.float32, device=dev)
+    n = min(CHUNK, total)
+    vd = torch.zeros(n, 3, dtype=torch.float32, device=dev)
+    vd[:, 2] = 1.0
+    for a in range(0, total, CHUNK):
+        b = min(a + CHUNK, total)
+        sg, _ = eng.mlp_fwd(blob, b - a, xyz=points(a, b), viewdir=vd)
+        sigma[a:b] = sg[:b - a]
+    return sigma
+
+
 class OccupancyGrid:
     def __init__(self, bits, G, center=(0.0, 0.0, 0.0), bound=0.5):
         G = int(G)
@@ -70,15 +87,7 @@ class OccupancyGrid:
         eng.ensure_packed(params, bwd=False)
         code = shape_code.detach().reshape(-1).to(dev, torch.float32).contiguous()
         blob, _ = eng.latent_fwd(params, code, torch.zeros_like(code))
-        sigma = torch.empty(Gs ** 3, dtype=torch.float32, device=dev)
-        n = min(CHUNK, Gs ** 3)
-        vd = torch.zeros(n, 3, dtype=torch.float32, device=dev)
-        vd[:, 2] = 1.0
-        for a in range(0, Gs ** 3, CHUNK):
-            b = min(a + CHUNK, Gs ** 3)
-            xyz = cls.cell_centers(Gs, center, bound, a, b, dev)
-            sg, _ = eng.mlp_fwd(blob, b - a, xyz=xyz, viewdir=vd)
-            sigma[a:b] = sg[:b - a]
+        sigma = eval_density(eng, blob, Gs ** 3, lambda a, b: cls.cell_centers(Gs, center, bound, a, b, dev))
         if s > 1:
             sigma = sigma.reshape(G, s, G, s, G, s).amax(dim=(1, 3, 5)).contiguous().reshape(-1)
         return cls(_eng.occupancy_build(sigma, int(G), tau, dilate), G, center, bound)

@@ -55,6 +55,13 @@ beyond it needs a larger ``occ_bound`` (DESIGN.md 8.4 has the figures).
 The optimisation steps are untouched: the codes move, so no grid is valid for
 them.  The grid's set share and the mean kept share of the samples are left in
 ``occ_fraction`` / ``occ_kept`` per object; ``codes.pth`` keeps its keys.
+``save_mesh=True`` (no reference counterpart) writes, after each object's
+optimisation, ``<save_dir>/<obj_id>/mesh.ply``: the surface density =
+``mesh_iso`` of the optimised codes on a ``mesh_grid``^3 lattice over
+[-mesh_bound, mesh_bound]^3 (None: (far - near) / 2, as the occupancy box),
+with normals and colours (``mesh.extract_mesh``).  ``mesh_iso``
+has no default: no value has been measured on a real model.  Nothing else
+changes: the mesh is taken after the evaluation, on rank 0.
 """
 import json
 import os
@@ -65,6 +72,7 @@ import torch
 
 from . import dp
 from .data import SRN, collate_one
+from .mesh import extract_mesh, write_ply
 from .metrics import image_metrics, psnr as mse_to_psnr, ssim_legacy
 from .model import CodeNeRF
 from .occupancy import OccupancyGrid
@@ -83,7 +91,8 @@ class Optimizer:
     def __init__(self, saved_dir, gpu=0, instance_ids=(), splits="test", jsonfile="srncar.json",
                  batch_size=2048, num_opts=200, hpams=None, exp_root="exps", dist=None, n_importance=None,
                  device_metrics=False, mask=None, bg_weight=0.0, sil_coef=0.0, sparse_eval=False, occ_grid=OCC_GRID,
-                 occ_tau=OCC_TAU, occ_dilate=OCC_DILATE, occ_bound=None):
+                 occ_tau=OCC_TAU, occ_dilate=OCC_DILATE, occ_bound=None, save_mesh=False, mesh_grid=128,
+                 mesh_iso=None, mesh_bound=None):
         self.hpams = hpams if hpams is not None else load_hpams(jsonfile)
         # fine samples per ray (the JSON's N_importance, as Trainer reads it;
         # n_importance overrides it); 0: the reference's coarse-only loop
@@ -110,6 +119,20 @@ class Optimizer:
         if self.occ_bound is not None and not self.occ_bound > 0:
             raise ValueError("occ_bound must be positive")
         self.occ_fraction, self.occ_kept = {}, {}
+        # a coloured mesh of every optimised object (module docstring)
+        self.save_mesh = bool(save_mesh)
+        self.mesh_grid = int(mesh_grid)
+        self.mesh_iso = None if mesh_iso is None else float(mesh_iso)
+        self.mesh_bound = None if mesh_bound is None else float(mesh_bound)
+        if self.save_mesh and self.mesh_iso is None:
+            raise ValueError("save_mesh needs mesh_iso: the density of the surface has no default")
+        if self.mesh_iso is not None and not np.isfinite(self.mesh_iso):
+            raise ValueError("mesh_iso must be finite")
+        if not 2 <= self.mesh_grid <= 512:
+            raise ValueError("mesh_grid must be in [2, 512]")
+        if self.mesh_bound is not None and not (self.mesh_bound > 0 and np.isfinite(self.mesh_bound)):
+            raise ValueError("mesh_bound must be positive")
+        self.mesh_counts = {}
         self.device = torch.device("cuda", int(gpu))
         torch.cuda.set_device(self.device)
         self.exp_root = exp_root
@@ -265,6 +288,19 @@ class Optimizer:
                 self.pose_rot_err[num_obj] = [e[0] for e in errs]
                 self.pose_trans_err[num_obj] = [e[1] for e in errs]
             self.save_opts(num_obj)
+            if self.save_mesh and self.rank == 0:
+                self.write_mesh(num_obj, shapecode, texturecode)
+
+    def write_mesh(self, num_obj, shapecode, texturecode):
+        """<save_dir>/<obj_id>/mesh.ply of the optimised codes (module docstring)."""
+        bound = self.mesh_bound if self.mesh_bound is not None else (self.hpams["far"] - self.hpams["near"]) / 2
+        m = extract_mesh(self.model, shapecode, texturecode, n=self.mesh_grid, bound=bound, iso=self.mesh_iso)
+        d = os.path.join(self.save_dir, str(self.ids[num_obj]))
+        os.makedirs(d, exist_ok=True)
+        write_ply(os.path.join(d, "mesh.ply"), m.verts, m.tris, m.normals, m.colors)
+        self.mesh_counts[num_obj] = (int(m.verts.shape[0]), int(m.tris.shape[0]))
+        print(f"object {num_obj}: mesh at density {self.mesh_iso:g} on {self.mesh_grid}^3 points: "
+              f"{m.verts.shape[0]} vertices, {m.tris.shape[0]} triangles")
 
     def _foreground(self, num_obj, imgs, instance_ids):
         """Foreground {0, 1} of every target view, (H*W,) each on the device,

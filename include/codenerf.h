@@ -367,6 +367,56 @@ int cn_sparse_scatter(const uint32_t *d_keep, const int *d_offset, int R, int N,
                       const float *d_sigma_k, const float *d_rgb_k, float *d_sigma, float *d_rgb,
                       void *stream);
 
+/* ---- iso-surface of a density lattice (additive to ABI 4; no reference
+ * counterpart): marching tetrahedra on the Kuhn (Freudenthal) triangulation,
+ * which has no ambiguous case, and whose face diagonals agree between
+ * neighbouring cubes, so the surface is closed wherever the field is outside
+ * on the lattice boundary.  DESIGN.md 8.5.
+ * Lattice: nx x ny x nz points, point (ix, iy, iz) is c = (ix ny + iy) nz + iz
+ * of d_field [P], P = nx ny nz.  A point is INSIDE iff !(field[c] < iso) (NaN:
+ * inside); its position is p_a = lo_a + float(i_a) s_a per axis, in float32
+ * with separately rounded operations.
+ * Edges: point p owns edge k = 0..6 towards p + e_k, e_k = ((m >> 2) & 1,
+ * (m >> 1) & 1, m & 1) with m = k + 1, when p + e_k is in the lattice.  An
+ * edge CROSSES when exactly one end is inside; d_vflags[c] has bit k set for a
+ * crossing owned edge and d_vcount[c] = popcount.  Each crossing edge carries
+ * one vertex, row voff[c] + popcount(vflags[c] & ((1 << k) - 1)), voff the
+ * exclusive prefix sum of vcount.  With a = p, b = p + e_k:
+ *   t = (iso - s_a) / (s_b - s_a)   (correctly rounded; NaN -> 0.5; clamped to
+ *   [0, 1]),   x = P_a + t (P_b - P_a)   per axis, separately rounded.
+ * Tetrahedra: the cube with lowest corner p (ix < nx - 1, iy < ny - 1, iz <
+ * nz - 1) is cut into 6, one per permutation pi of the axes (x, y, z) in
+ * lexicographic order: v0 = p, v1 = v0 + axis pi0, v2 = v1 + axis pi1, v3 = p +
+ * (1, 1, 1); edge (v_i, v_j), i < j, is an owned edge of v_i.  With the inside
+ * corners `ins` and the outside ones `out` ascending: 1 inside (a): the
+ * triangle [(a, o) for o in out]; 3 inside (o outside): [(i, o) for i in ins];
+ * 2 inside (a < b; c < d outside): [(a,c), (a,d), (b,d)] then [(a,c), (b,d),
+ * (b,c)].  Orientation, decided in the unit cube with every crossing at its
+ * edge's midpoint: with g = mean of the outside corners - mean of the inside
+ * corners, a triangle with ((q1 - q0) x (q2 - q0)) . g < 0 has its last two
+ * entries swapped, so normals point from inside to outside (towards lower
+ * density).  csrc/mesh_tables.h holds the resulting table, generated by
+ * tools/gen_mesh_tables.py.
+ * d_tcount[c]: triangles of the cube at c (at most 12; 0 where there is no
+ * cube).  The cube's triangles are rows toff[c] ... of d_tri, toff the
+ * exclusive prefix sum of tcount, in tetrahedron order, then in the order
+ * above; a row holds three vertex rows.  No atomics: every output element is
+ * written by exactly one thread.  The prefix sums are the caller's.
+ * Both entries return -1 with cn_last_error() naming the entry, before any
+ * device call, for a NULL pointer, a dimension outside [2, 1024], P > 2^27 (so
+ * that 7 P and 12 P fit an int32), iso NaN, a spacing that is not finite and
+ * positive, or a lo that is not finite.
+ *
+ * cn_mesh_count: d_vflags, d_vcount, d_tcount [P], every element written. */
+int cn_mesh_count(const float *d_field, int nx, int ny, int nz, float iso, uint8_t *d_vflags,
+                  int *d_vcount, int *d_tcount, void *stream);
+/* d_vflags as cn_mesh_count left it for the same field and iso; d_voff, d_toff
+ * [P] the exclusive prefix sums.  d_vert [Nv][3], d_tri [Nt][3] (Nv, Nt the
+ * totals): rows >= Nv of d_vert and rows >= Nt of d_tri are not written. */
+int cn_mesh_emit(const float *d_field, int nx, int ny, int nz, float iso, float lo_x, float lo_y,
+                 float lo_z, float s_x, float s_y, float s_z, const uint8_t *d_vflags,
+                 const int *d_voff, const int *d_toff, float *d_vert, int *d_tri, void *stream);
+
 /* ---- evaluation metrics of the test-time loop (additive to ABI 4) for V
  * views at once: the PSNR argument of src/optimizer.py:117-125 and SSIM as
  * src/optimizer.py:156 calls it (skimage structural_similarity(multichannel=

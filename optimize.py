@@ -6,6 +6,7 @@
          [--n_importance N] [--device_metrics True]
          [--mask {none,white,files} [--bg_weight 0] [--sil_coef 0]]
          [--sparse_eval True [--occ_grid 128] [--occ_tau 1e-1] [--occ_dilate 2] [--occ_bound B]]
+         [--save_mesh True --mesh_iso S [--mesh_grid 128] [--mesh_bound B]]
 
 --optimize_pose (no reference counterpart) refines every target view's camera
 pose together with the codes; the two noise flags perturb the dataset poses it
@@ -38,6 +39,12 @@ optimised shape code: --occ_grid cells per axis over [-B, B]^3 (--occ_bound,
 default (far - near) / 2), a cell set when the density at its centre reaches
 --occ_tau, dilated by --occ_dilate cells.  Samples in empty cells are not
 evaluated (density and colour 0); the optimisation steps are untouched.
+
+--save_mesh True (default False; no reference counterpart) writes a coloured
+triangle mesh of every optimised object to <save_dir>/<obj_id>/mesh.ply: the
+surface where the density equals --mesh_iso (required: it has no default) on a
+lattice of --mesh_grid points per axis over [-B, B]^3 (--mesh_bound, default
+(far - near) / 2), by marching tetrahedra, with per-vertex normals and colours.
 """
 import argparse
 import os
@@ -87,6 +94,13 @@ def build_parser():
                     help="dilate the occupied cells by this many cells (0 to 4)")
     ap.add_argument("--occ_bound", dest="occ_bound", type=float, default=None,
                     help="half edge of the grid's box around the origin (default (far - near) / 2)")
+    ap.add_argument("--save_mesh", dest="save_mesh", type=str2bool, default=False,
+                    help="write a coloured mesh.ply of every optimised object")
+    ap.add_argument("--mesh_grid", dest="mesh_grid", type=int, default=None, help="lattice points per axis")
+    ap.add_argument("--mesh_iso", dest="mesh_iso", type=float, default=None,
+                    help="density of the extracted surface (required with --save_mesh)")
+    ap.add_argument("--mesh_bound", dest="mesh_bound", type=float, default=None,
+                    help="half edge of the lattice's box around the origin (default (far - near) / 2)")
     return ap
 
 
@@ -100,7 +114,8 @@ def main():
                     int(args.num_opts), n_importance=args.n_importance, device_metrics=args.device_metrics,
                     mask=None if args.mask == "none" else args.mask, bg_weight=args.bg_weight,
                     sil_coef=args.sil_coef, sparse_eval=args.sparse_eval, occ_bound=args.occ_bound,
-                    **{k: getattr(args, k) for k in ("occ_grid", "occ_tau", "occ_dilate")
+                    save_mesh=args.save_mesh, mesh_iso=args.mesh_iso, mesh_bound=args.mesh_bound,
+                    **{k: getattr(args, k) for k in ("occ_grid", "occ_tau", "occ_dilate", "mesh_grid")
                        if getattr(args, k) is not None})
     if args.optimize_pose:
         noise = (args.pose_noise_deg, args.pose_noise_trans) if args.pose_noise_deg or args.pose_noise_trans else None
