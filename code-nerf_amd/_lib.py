@@ -83,6 +83,7 @@ _SIGS = {
     "cn_render_loss_fine_masked": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P,
                                         _P, _P, _P, _F, _P, _P]),
     "cn_composite_fine_fwd": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "cn_composite_aov": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "cn_occupancy_build": (_I, [_P, _I, _F, _I, _P, _P]),
     "cn_sparse_mark": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _F, _F, _F, _F, _I, _P, _P, _P]),
     "cn_sparse_gather": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),

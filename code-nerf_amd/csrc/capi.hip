@@ -17,6 +17,7 @@
 #include "metrics.hip"
 #include "sparse.hip"
 #include "mesh.hip"
+#include "aov.hip"
 #include "inputgrad.hip"
 #include "probe.hip"
 
@@ -672,6 +673,29 @@ int cn_composite_fine_fwd(const float* d_sigma_c, const float* d_rgb_c, const fl
                      d_z_c, zc_stride, Nc, d_sigma_f, d_rgb_f, d_z_f, Nf, R, white_bg, d_out_rgb, d_out_depth,
                      d_out_acc);
   return launch_check("composite_fine_fwd_kernel");
+}
+
+int cn_composite_aov(const float* d_sigma_c, const float* d_rgb_c, const float* d_z_c, int zc_stride, int Nc,
+                     const float* d_grad_c, const float* d_sigma_f, const float* d_rgb_f, const float* d_z_f, int Nf,
+                     const float* d_grad_f, int R, int white_bg, float* d_out_rgb, float* d_out_depth,
+                     float* d_out_acc, float* d_out_depth_med, float* d_out_normal, void* stream) {
+  if (!d_sigma_c || !d_rgb_c || !d_z_c || !d_out_rgb || !d_out_depth) return fail("cn_composite_aov: NULL argument");
+  if (Nc < 1 || Nf < 0) return fail("cn_composite_aov: Nc must be at least 1 and Nf at least 0");
+  if ((long long)Nc + Nf > 64 * kMaxPer) return fail("cn_composite_aov: at most 256 samples per ray");
+  if (zc_stride != 0 && zc_stride != Nc) return fail("cn_composite_aov: zc_stride must be 0 or Nc");
+  if (Nf > 0 && (!d_sigma_f || !d_rgb_f || !d_z_f))
+    return fail("cn_composite_aov: Nf > 0 needs d_sigma_f, d_rgb_f and d_z_f");
+  if (Nf == 0 && (d_sigma_f || d_rgb_f || d_z_f || d_grad_f))
+    return fail("cn_composite_aov: Nf == 0 takes no fine pointer");
+  if (d_out_normal && (!d_grad_c || (Nf > 0 && !d_grad_f)))
+    return fail("cn_composite_aov: d_out_normal needs d_grad_c (and d_grad_f when Nf > 0)");
+  if (!d_out_normal && (d_grad_c || d_grad_f)) return fail("cn_composite_aov: a gradient pointer needs d_out_normal");
+  if (check_rn(R, Nc + Nf, "cn_composite_aov")) return -1;
+  const AovArgs a{d_sigma_c, d_rgb_c, d_z_c, zc_stride, Nc, d_grad_c, d_sigma_f, d_rgb_f, d_z_f, Nf, d_grad_f,
+                  R, white_bg, d_out_rgb, d_out_depth, d_out_acc, d_out_depth_med, d_out_normal};
+  if (Nf > 0) hipLaunchKernelGGL(composite_aov_kernel<true>, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), a);
+  else hipLaunchKernelGGL(composite_aov_kernel<false>, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), a);
+  return launch_check("composite_aov_kernel");
 }
 
 // Host checks shared by the occupancy-grid entries (no device call).

@@ -352,6 +352,27 @@ def composite_fine_fwd(sigma_c, rgb_c, z_c, Nc, sigma_f, rgb_f, z_f, Nf, R, whit
     return (out_rgb, depth, out_acc) if acc else (out_rgb, depth)
 
 
+def composite_aov(sigma_c, rgb_c, z_c, Nc, R, white_bg=True, grad_c=None, sigma_f=None, rgb_f=None, z_f=None, Nf=0,
+                  grad_f=None, acc=True, depth_median=True):
+    """composite_fwd (Nf 0) or composite_fine_fwd with the geometry buffers
+    (cn_composite_aov): -> dict(rgb (R,3), depth (R,), acc (R,) or None,
+    depth_median (R,) or None, normal (R,3) or None).  grad_c (R*Nc, 3) and,
+    with Nf > 0, grad_f (R*Nf, 3) = d sigma / d xyz per sample ask for the
+    normal sum_k w_k u_k (not normalised)."""
+    L = _lib.lib()
+    dev = sigma_c.device
+    zc_stride = 0 if z_c.numel() == Nc else Nc
+    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    out = dict(rgb=new(R, 3), depth=new(R), acc=new(R) if acc else None,
+               depth_median=new(R) if depth_median else None,
+               normal=new(R, 3) if grad_c is not None or grad_f is not None else None)
+    check(L.cn_composite_aov(ptr(sigma_c), ptr(rgb_c), ptr(z_c), zc_stride, int(Nc), ptr(grad_c), ptr(sigma_f),
+                             ptr(rgb_f), ptr(z_f), int(Nf), ptr(grad_f), int(R), int(white_bg), ptr(out["rgb"]),
+                             ptr(out["depth"]), ptr(out["acc"]), ptr(out["depth_median"]), ptr(out["normal"]),
+                             _dev_stream(sigma_c)), "cn_composite_aov")
+    return out
+
+
 def occupancy_build(sigma, G, tau, dilate=0):
     """Grid bits (G^3 / 32 words, int32 storage) from the densities at the G^3
     cell centres: sigma >= tau (NaN occupied), dilated by `dilate` cells

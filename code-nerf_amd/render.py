@@ -60,6 +60,7 @@ class ImageStep:
         self.last_acc = None                     # per-ray opacity of the last masked loss (ray_weight / acc_target)
         self.last_sparse = None                  # (kept coarse, kept fine, total) samples of the last render through a grid
         self._ws = {}                            # device -> grow-only workspace
+        self._aov_ws = {}                        # device -> grow-only workspace of render_aov's normals
         self._side = {}                          # device -> side stream
         # called whenever a step starts writing .grad (dp.GradExchange's
         # mark_dirty: a fused zero-grad AdamW step must not mask them)
@@ -503,6 +504,105 @@ class ImageStep:
         if occ is not None:
             self.last_sparse = (kept_c, kept_f, R * (Nc + Nf))
         return self._cat(rgbs), self._cat(depths)
+
+    def _aov_workspace(self, eng, M):
+        """What the normals of render_aov need for M rows (grow-only, per
+        device): the activation workspace, the network outputs and the constant
+        upstream gradient d sigma = 1, d rgb = 0."""
+        ws = self._aov_ws.get(eng.device)
+        if ws is None or ws["cap"] < M:
+            self._aov_ws.pop(eng.device, None)
+            del ws
+            cap, dev = eng.pad(M), eng.device
+            ws = dict(cap=cap, act=eng.new_act(cap),
+                      sig=torch.empty(cap, dtype=torch.float32, device=dev),
+                      rgb=torch.empty(cap, 3, dtype=torch.float32, device=dev),
+                      dsig=torch.ones(cap, dtype=torch.float32, device=dev),
+                      drgb=torch.zeros(cap, 3, dtype=torch.float32, device=dev))
+            self._aov_ws[eng.device] = ws
+        return ws
+
+    @torch.no_grad()
+    def render_aov(self, rays_o, viewdirs, z_c, shape_code, texture_code, n_fine=0, normals=True, rand_f=None,
+                   z_f=None):
+        """render (n_fine 0) or render_fine with the geometry buffers (no
+        reference counterpart) -> dict(rgb (R,3), depth (R,),
+        acc (R,), depth_median (R,), normal (R,3) or None): rgb and depth are
+        those calls' bit for bit; acc = sum w; depth_median = the z of the first
+        sample at which the running weight sum reaches 0.5; normal = sum_k w_k
+        u_k with u = -grad(sigma) / |grad(sigma)| per sample, not normalised
+        (engine.composite_aov).  rand_f, z_f and ``self.last_z_f``: as in
+        render_fine.
+        normals: each ray part runs the codes-mode forward in ray mode into a
+        workspace (coarse rows, then fine rows, as the steps lay them out) --
+        its sigma and rgb are the inference forward's bit for bit
+        (tests/test_gpu_aov.py), so it is the part's only forward --, the pose
+        backward with d sigma = 1 and d rgb = 0, and the input gradient of the
+        coarse and of the fine rows; the parts are then also sized to fit
+        engine.ACT_BUDGET.  False: no workspace and no backward."""
+        eng = self.model.engine()
+        params = self.model.param_list()
+        R, Nc, Nf = rays_o.shape[0], z_c.shape[-1], int(n_fine)
+        z = z_c.contiguous().to(eng.device, torch.float32)
+        if z_f is not None:
+            z_f = z_f.contiguous().to(eng.device, torch.float32)
+        elif rand_f is not None:
+            rand_f = rand_f.contiguous().to(eng.device, torch.float32)
+        eng.ensure_packed(params, bwd=bool(normals))
+        blob, _ = eng.latent_fwd(params, shape_code.reshape(-1).contiguous(), texture_code.reshape(-1).contiguous())
+        per = max(1, (eng.L.cn_max_samples() - 256) // max(Nc, Nf))
+        if normals:
+            cap = eng.max_act_samples(self.act_budget)
+            if (cap - 256) // (Nc + Nf) < 1:
+                raise ValueError(f"one ray of {Nc + Nf} samples does not fit the activation budget ({cap} samples): "
+                                 "raise CODENERF_ACT_BUDGET")
+            per = min(per, (cap - 256) // (Nc + Nf))
+        zc_stride = 0 if z.dim() == 1 else Nc
+        parts, zfs = [], []
+        for a in range(0, R, per):
+            b = min(a + per, R)
+            n = b - a
+            ro, vd = rays_o[a:b], viewdirs[a:b]
+            zp = z if z.dim() == 1 else z[a:b]
+            Mc, Mf = n * Nc, n * Nf
+            Mc_p = eng.pad(Mc)
+            ws = self._aov_workspace(eng, Mc_p + Mf if Nf else Mc) if normals else None
+
+            def fwd(m, zz, stride, N, r0):
+                if ws is None:
+                    return eng.mlp_fwd(blob, m, rays_o=ro, rays_d=vd, z=zz, z_stride=stride, n_samples=N)
+                rows = slice(r0, r0 + eng.pad(m))
+                return eng.mlp_fwd(blob, m, rays_o=ro, rays_d=vd, z=zz, z_stride=stride, n_samples=N, act=ws["act"],
+                                   act_M=ws["cap"], act_row0=r0, sigma=ws["sig"][rows], rgb=ws["rgb"][rows],
+                                   codes=True)
+
+            def grad(m, zz, stride, N, r0):
+                return eng.mlp_input_grad(ws["act"], m, rays_o=ro, rays_d=vd, z=zz, z_stride=stride, n_samples=N,
+                                          act_M=ws["cap"], row0=r0, per_ray=False)[0]
+
+            sig_c, rgb_c = fwd(Mc, zp, zc_stride, Nc, 0)
+            fine = {}
+            if Nf:
+                if z_f is not None:
+                    zf = z_f[a:b]
+                else:
+                    rnd = (torch.full((n, Nf), 0.5, dtype=torch.float32, device=eng.device) if rand_f is None
+                           else rand_f[a:b])
+                    zf = _eng.sample_pdf(sig_c, zp, n, Nc, rnd)
+                sig_f, rgb_f = fwd(Mf, zf, Nf, Nf, Mc_p)
+                fine = dict(sigma_f=sig_f, rgb_f=rgb_f, z_f=zf, Nf=Nf)
+                zfs.append(zf)
+            if normals:
+                # one pose backward over the coarse rows, the padding and the fine rows
+                eng.mlp_bwd(blob, Mc_p + Mf if Nf else Mc, ws["dsig"], ws["drgb"], ws["act"], act_M=ws["cap"],
+                            row0=0, pose=True)
+                fine.update(grad_c=grad(Mc, zp, zc_stride, Nc, 0))
+                if Nf:
+                    fine.update(grad_f=grad(Mf, zf, Nf, Nf, Mc_p))
+            parts.append(_eng.composite_aov(sig_c, rgb_c, zp, Nc, n, self.white_bg, **fine))
+        if Nf:
+            self.last_z_f = self._cat(zfs)
+        return {k: None if parts[0][k] is None else self._cat([p[k] for p in parts]) for k in parts[0]}
 
     @torch.no_grad()
     def render_sharded(self, rays_o, viewdirs, z_vals, shape_code, texture_code, dist=None, group=None):

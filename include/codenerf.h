@@ -324,6 +324,37 @@ int cn_composite_fine_fwd(const float *d_sigma_c, const float *d_rgb_c, const fl
                           const float *d_z_f, int Nf, int R, int white_bg, float *d_out_rgb,
                           float *d_out_depth, float *d_out_acc, void *stream);
 
+/* ---- geometry buffers of a composited ray (additive to ABI 4; no reference
+ * counterpart).  cn_composite_fwd (Nf == 0, the three fine
+ * pointers and d_grad_f NULL) or cn_composite_fine_fwd (Nf > 0, the same merge)
+ * with two more outputs.  Over the ray's (merged) samples k = 0 .. N-1 with
+ * the compositing weights w_k:
+ *   d_out_rgb [R][3], d_out_depth [R], d_out_acc [R] (may be NULL): those
+ *     entries' rgb, depth = sum w z and weight sum, bit for bit;
+ *   d_out_depth_med [R] (may be NULL): z_m of the first sample m with C_m >=
+ *     0.5, C_k the running float64 sum of w_j, j <= k, in sample order; z_{N-1}
+ *     when the ray never gets there (the closing interval puts the leftover
+ *     transmittance at the last sample, so only non-finite weights do that);
+ *   d_out_normal [R][3] (may be NULL): sum_k w_k u_k, NOT normalised (its
+ *     length is at most acc and says how much surface the ray met), with u_k =
+ *     -g_k / |g_k| in float32 and (0, 0, 0) unless |g_k| > 0; g = d sigma / d
+ *     xyz per sample, d_grad_c [R*Nc][3] and d_grad_f [R*Nf][3] (what
+ *     cn_mlp_bwd_pose with d sigma = 1, d rgb = 0 and cn_mlp_input_grad leave
+ *     in d_dxyz).  Products rounded to float32, summed in float64 in a fixed
+ *     order, rounded once.
+ * No atomics; every output is deterministic and independent of which optional
+ * pointers are NULL.  Returns -1 with a message starting "cn_composite_aov:",
+ * before any launch, for: a NULL required pointer; Nc < 1 or Nf < 0; Nc + Nf >
+ * 256; zc_stride other than 0 or Nc; Nf > 0 with a NULL fine pointer; Nf == 0
+ * with a fine pointer given; d_out_normal without d_grad_c (and d_grad_f when
+ * Nf > 0); a gradient pointer without d_out_normal; R < 1 or R * (Nc + Nf) >
+ * CN_MAX_SAMPLES. */
+int cn_composite_aov(const float *d_sigma_c, const float *d_rgb_c, const float *d_z_c, int zc_stride,
+                     int Nc, const float *d_grad_c, const float *d_sigma_f, const float *d_rgb_f,
+                     const float *d_z_f, int Nf, const float *d_grad_f, int R, int white_bg,
+                     float *d_out_rgb, float *d_out_depth, float *d_out_acc,
+                     float *d_out_depth_med, float *d_out_normal, void *stream);
+
 /* ---- rendering through an occupancy grid (additive to ABI 4; no reference
  * counterpart).  The grid is G^3 cells (G a multiple of 32 in [32, 256]) over
  * the box [lo, lo + G / inv_cell)^3, one bit per cell: cell c = (ix G + iy) G
