@@ -88,6 +88,10 @@ _SIGS = {
     "cn_sparse_mark": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _F, _F, _F, _F, _I, _P, _P, _P]),
     "cn_sparse_gather": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "cn_sparse_scatter": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "cn_scene_rays": (_I, [_P, _P, _I, _P, _I, _P, _P, _P]),
+    "cn_scene_combine": (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
+    "cn_scene_composite": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P,
+                                _P]),
     "cn_mesh_count": (_I, [_P, _I, _I, _I, _F, _P, _P, _P, _P]),
     "cn_mesh_emit": (_I, [_P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P]),
     "cn_image_metrics_ws_bytes": (_Z, [_I, _I, _I, _I]),

@@ -18,6 +18,7 @@
 #include "sparse.hip"
 #include "mesh.hip"
 #include "aov.hip"
+#include "scene.hip"
 #include "inputgrad.hip"
 #include "probe.hip"
 
@@ -696,6 +697,85 @@ int cn_composite_aov(const float* d_sigma_c, const float* d_rgb_c, const float* 
   if (Nf > 0) hipLaunchKernelGGL(composite_aov_kernel<true>, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), a);
   else hipLaunchKernelGGL(composite_aov_kernel<false>, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), a);
   return launch_check("composite_aov_kernel");
+}
+
+// Host checks shared by the scene entries (no device call).
+static int check_scene_k(int K, const char* who) {
+  if (K < 1 || K > kMaxObjects) return fail(std::string(who) + ": K must be in [1, 8]");
+  return 0;
+}
+static int check_inv_s(float v, const char* who) {
+  if (!std::isfinite(v) || !(v > 0.f)) return fail(std::string(who) + ": 1/s must be finite and positive");
+  return 0;
+}
+
+int cn_scene_rays(const float* d_rays_o, const float* d_rays_d, int R, const float* h_xf, int K, float* d_out_o,
+                  float* d_out_d, void* stream) {
+  if (!d_rays_o || !d_rays_d || !h_xf || !d_out_o || !d_out_d) return fail("cn_scene_rays: NULL argument");
+  if (check_scene_k(K, "cn_scene_rays")) return -1;
+  if (R < 1) return fail("cn_scene_rays: R must be at least 1");
+  if (check_samples(R, "cn_scene_rays")) return -1;
+  SceneXfs xf = {};
+  for (int k = 0; k < K; ++k) {
+    const float* h = h_xf + 13 * k;
+    for (int i = 0; i < 12; ++i)
+      if (!std::isfinite(h[i])) return fail("cn_scene_rays: the rotation and the translation must be finite");
+    if (check_inv_s(h[12], "cn_scene_rays")) return -1;
+    std::copy(h, h + 9, xf.x[k].R);
+    std::copy(h + 9, h + 12, xf.x[k].t);
+    xf.x[k].inv_s = h[12];
+  }
+  hipLaunchKernelGGL(scene_rays_kernel, dim3(grid_for(R, 256), K), dim3(256), 0, S(stream), d_rays_o, d_rays_d, R, xf,
+                     d_out_o, d_out_d);
+  return launch_check("scene_rays_kernel");
+}
+
+int cn_scene_combine(const float* d_sigma_k, const float* d_rgb_k, const float* h_inv_s, int K, int M, float* d_sigma,
+                     float* d_rgb, void* stream) {
+  if (!d_sigma_k || !d_rgb_k || !h_inv_s || !d_sigma || !d_rgb) return fail("cn_scene_combine: NULL argument");
+  if (check_scene_k(K, "cn_scene_combine")) return -1;
+  if (check_samples(M, "cn_scene_combine")) return -1;
+  SceneInvS inv_s = {};
+  for (int k = 0; k < K; ++k) {
+    if (check_inv_s(h_inv_s[k], "cn_scene_combine")) return -1;
+    inv_s.v[k] = h_inv_s[k];
+  }
+  hipLaunchKernelGGL(scene_combine_kernel, dim3(grid_for(M, 256)), dim3(256), 0, S(stream), d_sigma_k, d_rgb_k, inv_s,
+                     K, M, d_sigma, d_rgb);
+  return launch_check("scene_combine_kernel");
+}
+
+int cn_scene_composite(const float* d_sigma_c, const float* d_rgb_c, const float* d_z_c, int zc_stride, int Nc,
+                       const float* d_sigma_f, const float* d_rgb_f, const float* d_z_f, int Nf, const float* d_obj_c,
+                       const float* d_obj_f, const float* h_inv_s, int K, int R, int white_bg, float acc_min,
+                       float* d_out_rgb, float* d_out_depth, float* d_out_acc, float* d_obj_acc, int* d_instance,
+                       void* stream) {
+  if (!d_sigma_c || !d_rgb_c || !d_z_c || !h_inv_s || !d_out_rgb || !d_out_depth || !d_out_acc)
+    return fail("cn_scene_composite: NULL argument");
+  if (check_scene_k(K, "cn_scene_composite")) return -1;
+  if (Nc < 1 || Nf < 0) return fail("cn_scene_composite: Nc must be at least 1 and Nf at least 0");
+  if ((long long)Nc + Nf > 64 * kMaxPer) return fail("cn_scene_composite: at most 256 samples per ray");
+  if (zc_stride != 0 && zc_stride != Nc) return fail("cn_scene_composite: zc_stride must be 0 or Nc");
+  if (Nf > 0 && (!d_sigma_f || !d_rgb_f || !d_z_f))
+    return fail("cn_scene_composite: Nf > 0 needs d_sigma_f, d_rgb_f and d_z_f");
+  if (Nf == 0 && (d_sigma_f || d_rgb_f || d_z_f || d_obj_f))
+    return fail("cn_scene_composite: Nf == 0 takes no fine pointer");
+  if ((d_obj_acc == nullptr) != (d_instance == nullptr))
+    return fail("cn_scene_composite: d_obj_acc and d_instance go together");
+  if (d_obj_acc && (!d_obj_c || (Nf > 0 && !d_obj_f)))
+    return fail("cn_scene_composite: the labels need d_obj_c (and d_obj_f when Nf > 0)");
+  SceneInvS inv_s = {};
+  for (int k = 0; k < K; ++k) {
+    if (check_inv_s(h_inv_s[k], "cn_scene_composite")) return -1;
+    inv_s.v[k] = h_inv_s[k];
+  }
+  if (std::isnan(acc_min)) return fail("cn_scene_composite: acc_min is NaN");
+  if (check_rn(R, Nc + Nf, "cn_scene_composite")) return -1;
+  const SceneCompositeArgs a{d_sigma_c, d_rgb_c, d_z_c, zc_stride, Nc, d_sigma_f, d_rgb_f, d_z_f, Nf, d_obj_c, d_obj_f,
+                             inv_s, K, R, white_bg, acc_min, d_out_rgb, d_out_depth, d_out_acc, d_obj_acc, d_instance};
+  if (Nf > 0) hipLaunchKernelGGL(scene_composite_kernel<true>, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), a);
+  else hipLaunchKernelGGL(scene_composite_kernel<false>, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), a);
+  return launch_check("scene_composite_kernel");
 }
 
 // Host checks shared by the occupancy-grid entries (no device call).

@@ -427,6 +427,68 @@ def sparse_scatter(keep, offset, R, N, sigma_k, rgb_k, sigma=None, rgb=None):
     return sigma, rgb
 
 
+def _host_floats(vals):
+    """A host float array for an h_* argument -> (keep-alive, pointer)."""
+    a = (ctypes.c_float * len(vals))(*[float(v) for v in vals])
+    return a, ctypes.cast(a, ctypes.c_void_p)
+
+
+def scene_rays(rays_o, rays_d, transforms):
+    """World rays in each object's frame (cn_scene_rays).  transforms: K rows of
+    13 floats, the object -> world rotation row-major, the translation and
+    1 / scale.  -> (origins (K, R, 3), directions (K, R, 3))."""
+    L = _lib.lib()
+    K, R = len(transforms), rays_o.shape[0]
+    flat = [v for row in transforms for v in row]
+    if len(flat) != 13 * K:
+        raise ValueError("scene_rays: a transform is 13 floats (rotation 9, translation 3, 1 / scale)")
+    out_o = torch.empty(K, R, 3, dtype=torch.float32, device=rays_o.device)
+    out_d = torch.empty(K, R, 3, dtype=torch.float32, device=rays_o.device)
+    keep, h = _host_floats(flat)
+    check(L.cn_scene_rays(ptr(rays_o), ptr(rays_d), R, h, K, ptr(out_o), ptr(out_d), _dev_stream(rays_o)),
+          "cn_scene_rays")
+    return out_o, out_d
+
+
+def scene_combine(sigma_k, rgb_k, inv_s, sigma=None, rgb=None):
+    """The K object planes sigma_k (K, M) and rgb_k (K, M, 3) as one
+    (cn_scene_combine); inv_s: K host floats 1 / scale.  -> (sigma (M,), rgb (M, 3))."""
+    L = _lib.lib()
+    K, M = len(inv_s), sigma_k.numel() // max(1, len(inv_s))
+    if sigma_k.numel() != K * M or rgb_k.numel() != 3 * K * M:
+        raise ValueError("scene_combine: sigma_k must hold K * M and rgb_k 3 * K * M values")
+    if sigma is None:
+        sigma = torch.empty(M, dtype=torch.float32, device=sigma_k.device)
+    if rgb is None:
+        rgb = torch.empty(M, 3, dtype=torch.float32, device=sigma_k.device)
+    keep, h = _host_floats(inv_s)
+    check(L.cn_scene_combine(ptr(sigma_k), ptr(rgb_k), h, K, M, ptr(sigma), ptr(rgb), _dev_stream(sigma_k)),
+          "cn_scene_combine")
+    return sigma, rgb
+
+
+def scene_composite(sigma_c, rgb_c, z_c, Nc, R, inv_s, white_bg=True, sigma_f=None, rgb_f=None, z_f=None, Nf=0,
+                    obj_c=None, obj_f=None, labels=True, acc_min=0.5):
+    """composite_fwd (Nf 0) or composite_fine_fwd on a scene's combined planes,
+    with the weights split back onto the K objects (cn_scene_composite): obj_c
+    (K, R*Nc) and obj_f (K, R*Nf) are the object density planes that went into
+    scene_combine.  -> dict(rgb (R,3), depth (R,), acc (R,), obj_acc (R, K) and
+    instance (R,) int32, both None without labels)."""
+    L = _lib.lib()
+    dev = sigma_c.device
+    K = len(inv_s)
+    zc_stride = 0 if z_c.numel() == Nc else Nc
+    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    out = dict(rgb=new(R, 3), depth=new(R), acc=new(R), obj_acc=new(R, K) if labels else None,
+               instance=torch.empty(R, dtype=torch.int32, device=dev) if labels else None)
+    keep, h = _host_floats(inv_s)
+    check(L.cn_scene_composite(ptr(sigma_c), ptr(rgb_c), ptr(z_c), zc_stride, int(Nc), ptr(sigma_f), ptr(rgb_f),
+                               ptr(z_f), int(Nf), ptr(obj_c), ptr(obj_f), h, K, int(R), int(white_bg), float(acc_min),
+                               ptr(out["rgb"]), ptr(out["depth"]), ptr(out["acc"]), ptr(out["obj_acc"]),
+                               ptr(out["instance"]), _dev_stream(sigma_c)), "cn_scene_composite")
+    return out
+
+
 def _mesh_field(field, dims, who):
     nx, ny, nz = (int(n) for n in dims)
     if field.dtype != torch.float32 or not field.is_contiguous() or field.numel() != nx * ny * nz:

@@ -69,6 +69,11 @@ class OccupancyGrid:
         return lo + (idx + 0.5) * cell
 
     @classmethod
+    def full(cls, G=32, bound=0.5, center=(0.0, 0.0, 0.0), device=None):
+        """Every cell set: the box [center - bound, center + bound)^3 alone."""
+        return cls(torch.full((int(G) ** 3 // 32,), -1, dtype=torch.int32, device=device), G, center, bound)
+
+    @classmethod
     def build(cls, model, shape_code, G=128, bound=0.5, center=(0.0, 0.0, 0.0), tau=1e-1, dilate=2, supersample=1):
         """The grid of ``model`` under ``shape_code``: the model's own plan is
         evaluated at the centres of a (G supersample)^3 lattice (explicit

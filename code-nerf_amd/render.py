@@ -432,21 +432,24 @@ class ImageStep:
         (a ray whose last merged sample is culled is not opaque)."""
         return self._render(rays_o, viewdirs, z_c, int(n_fine), shape_code, texture_code, rand_f, z_f, occupancy)
 
-    def _sparse_fwd(self, eng, blob, rays_o, viewdirs, z, n, N, occ, keep_last):
+    def _sparse_fwd(self, eng, blob, rays_o, viewdirs, z, n, N, occ, keep_last, out_sig=None, out_rgb=None):
         """The MLP pass of one ray part through the grid: mark -> prefix sum ->
         gather -> MLP on the kept points -> scatter.  -> (sigma (n N,), rgb
-        (n N, 3), kept samples); reading the kept count back synchronises."""
+        (n N, 3), kept samples); reading the kept count back synchronises.
+        out_sig / out_rgb: the planes to scatter into (render_scene's slices)."""
         keep, count = _eng.sparse_mark(rays_o, viewdirs, z, n, N, occ.bits, occ.G, occ.lo, occ.inv_cell, keep_last)
         incl = torch.cumsum(count, 0, dtype=torch.int32)
         Mk = int(incl[-1])                       # cn_mlp_fwd takes its sample count on the host
         if Mk == 0:
+            if out_sig is not None:
+                return out_sig.zero_(), out_rgb.zero_(), 0
             dev = rays_o.device
             return (torch.zeros(n * N, dtype=torch.float32, device=dev),
                     torch.zeros(n * N, 3, dtype=torch.float32, device=dev), 0)
         off = incl - count
         xyz, vd = _eng.sparse_gather(rays_o, viewdirs, z, n, N, keep, off, Mk)
         sig_k, rgb_k = eng.mlp_fwd(blob, Mk, xyz=xyz, viewdir=vd)
-        sig, rgb = _eng.sparse_scatter(keep, off, n, N, sig_k, rgb_k)
+        sig, rgb = _eng.sparse_scatter(keep, off, n, N, sig_k, rgb_k, out_sig, out_rgb)
         return sig, rgb, Mk
 
     def _render(self, rays_o, viewdirs, z_c, Nf, shape_code, texture_code, rand_f=None, z_f=None, occupancy=None):
@@ -504,6 +507,76 @@ class ImageStep:
         if occ is not None:
             self.last_sparse = (kept_c, kept_f, R * (Nc + Nf))
         return self._cat(rgbs), self._cat(depths)
+
+    @torch.no_grad()
+    def render_scene(self, rays_o, viewdirs, z_c, scene, n_fine=0, rand_f=None, labels=True, acc_min=0.5):
+        """Several objects in one picture (``scene.Scene``; no reference
+        counterpart) -> dict(rgb (R,3), depth (R,), acc (R,),
+        obj_acc (R, K), instance (R,) int32; the last two None without labels).
+        Object k sees the world ray from its own frame (engine.scene_rays) at
+        the depths z / s_k and is evaluated only at the samples in set cells of
+        its grid -- no sample is exempt, so it contributes nothing outside its
+        box --; the K planes are combined per sample (engine.scene_combine) and
+        the ray is composited as one object's: coarse only, or with n_fine
+        samples of sample_pdf on the combined coarse density (rand_f None: the
+        deterministic ones), merged.  obj_acc[k] = sum_i w_i f_k,i, the share of
+        the ray's opacity that object k holds; instance = the lowest k with the
+        largest share where acc >= acc_min, else -1.
+        ``self.last_z_f`` and ``self.last_sparse`` as render_fine leaves them,
+        the kept counts summed over the objects (total = K R (Nc + Nf)).  One
+        host synchronisation per object and pass.  No gradients."""
+        eng = self.model.engine()
+        params = self.model.param_list()
+        dev = eng.device
+        objs = scene.objects
+        K, R, Nc, Nf = len(objs), rays_o.shape[0], z_c.shape[-1], int(n_fine)
+        z = z_c.contiguous().to(dev, torch.float32)
+        if rand_f is not None:
+            rand_f = rand_f.contiguous().to(dev, torch.float32)
+        rays_o = rays_o.contiguous().to(dev, torch.float32)
+        viewdirs = viewdirs.contiguous().to(dev, torch.float32)
+        eng.ensure_packed(params, bwd=False)
+        code = lambda c: c.detach().reshape(-1).to(dev, torch.float32).contiguous()
+        blobs = [eng.latent_fwd(params, code(o.shape_code), code(o.texture_code))[0] for o in objs]
+        xf, inv_s = scene.transforms(), scene.inv_s()
+        per = max(1, (eng.L.cn_max_samples() - 256) // max(Nc, Nf))
+        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        parts, zfs = [], []
+        kept_c = kept_f = 0
+
+        def one_pass(ro_k, rd_k, zz, n, N):
+            """The K objects over one set of depths -> (object densities (K, n N),
+            combined sigma, combined rgb, kept samples)."""
+            sig_k, rgb_k, kept = new(K, n * N), new(K, n * N, 3), 0
+            for k, o in enumerate(objs):
+                zk = zz if inv_s[k] == 1.0 else zz * inv_s[k]
+                kept += self._sparse_fwd(eng, blobs[k], ro_k[k], rd_k[k], zk, n, N, o.grid, False, sig_k[k],
+                                         rgb_k[k])[2]
+            sig, rgb = _eng.scene_combine(sig_k, rgb_k, inv_s)
+            return sig_k, sig, rgb, kept
+
+        for a in range(0, R, per):
+            b = min(a + per, R)
+            n = b - a
+            zp = z if z.dim() == 1 else z[a:b]
+            ro_k, rd_k = _eng.scene_rays(rays_o[a:b], viewdirs[a:b], xf)
+            obj_c, sig_c, rgb_c, k = one_pass(ro_k, rd_k, zp, n, Nc)
+            kept_c += k
+            fine = {}
+            if Nf:
+                rnd = (torch.full((n, Nf), 0.5, dtype=torch.float32, device=dev) if rand_f is None else rand_f[a:b])
+                zf = _eng.sample_pdf(sig_c, zp, n, Nc, rnd)
+                obj_f, sig_f, rgb_f, k = one_pass(ro_k, rd_k, zf, n, Nf)
+                kept_f += k
+                fine = dict(sigma_f=sig_f, rgb_f=rgb_f, z_f=zf, Nf=Nf, obj_f=obj_f if labels else None)
+                zfs.append(zf)
+            parts.append(_eng.scene_composite(sig_c, rgb_c, zp, Nc, n, inv_s, self.white_bg,
+                                              obj_c=obj_c if labels else None, labels=labels, acc_min=acc_min,
+                                              **fine))
+        if Nf:
+            self.last_z_f = self._cat(zfs)
+        self.last_sparse = (kept_c, kept_f, K * R * (Nc + Nf))
+        return {k: None if parts[0][k] is None else self._cat([p[k] for p in parts]) for k in parts[0]}
 
     def _aov_workspace(self, eng, M):
         """What the normals of render_aov need for M rows (grow-only, per

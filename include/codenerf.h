@@ -398,6 +398,63 @@ int cn_sparse_scatter(const uint32_t *d_keep, const int *d_offset, int R, int N,
                       const float *d_sigma_k, const float *d_rgb_k, float *d_sigma, float *d_rgb,
                       void *stream);
 
+/* ---- several objects in one scene (additive to ABI 4; no reference
+ * counterpart).  A scene is K objects, 1 <= K <= 8; object k has
+ * its own codes and occupancy grid and a similarity transform from its frame to
+ * the world: rotation R_k, translation t_k, scale s_k > 0.  Its field is
+ * evaluated on the world ray seen from its frame, at the sample depths z / s_k,
+ * through mark (keep_last 0) -> gather -> cn_mlp_fwd -> scatter; outside the
+ * set cells of its grid its density and colour are 0.  With a_k = sigma_k / s_k
+ * (the opacity sigma * delta does not depend on the scale) the scene's sample is
+ *   sigma = sum_k a_k,  f_k = a_k / sigma (0 unless sigma > 0),
+ *   rgb = sum_k f_k rgb_k,
+ * composited as one object's.  Every float32 operation of the three entries is
+ * rounded separately, in the order given; the division is correctly rounded.
+ * No atomics: every output element is written by one lane.  The host arrays
+ * (h_*) are read at the call.  Each entry returns -1 with a message starting
+ * with its name, before any launch, for a NULL required pointer, K outside
+ * [1, 8], a 1/s that is not finite and positive, or a size above
+ * CN_MAX_SAMPLES, and for what its own comment lists.
+ *
+ * cn_scene_rays: h_xf [K][13] = R_k row-major (9), t_k (3), 1 / s_k, all
+ * finite.  d_out_o, d_out_d [K][R][3], with q = o - t:
+ *   o_k,a = ((R_0a q_0 + R_1a q_1) + R_2a q_2) * (1 / s_k)
+ *   d_k,a = (R_0a d_0 + R_1a d_1) + R_2a d_2        (not re-normalised)
+ * i.e. R^T (o - t) / s and R^T d; the identity with s = 1 hands o and d back
+ * unchanged up to the sign of a zero.  Also refused: R < 1. */
+int cn_scene_rays(const float *d_rays_o, const float *d_rays_d, int R, const float *h_xf, int K,
+                  float *d_out_o, float *d_out_d, void *stream);
+/* d_sigma_k [K][M], d_rgb_k [K][M][3], h_inv_s [K] = 1 / s_k -> d_sigma [M],
+ * d_rgb [M][3] by the rule above, a_k = sigma_k * (1 / s_k), both sums left to
+ * right over k starting from the first term; rgb is 0 unless sigma > 0 (a NaN
+ * sum included).  With K = 1 and s = 1 the outputs are the inputs bit for bit
+ * wherever sigma > 0.  Also refused: M < 1. */
+int cn_scene_combine(const float *d_sigma_k, const float *d_rgb_k, const float *h_inv_s, int K,
+                     int M, float *d_sigma, float *d_rgb, void *stream);
+/* cn_composite_fwd (Nf == 0, every fine pointer NULL) or cn_composite_fine_fwd
+ * on the combined planes, bit for bit: d_out_rgb [R][3], d_out_depth [R],
+ * d_out_acc [R] (all required).  With the compositing weights w_i of the ray's
+ * (merged) samples:
+ *   d_obj_acc [R][K]: sum_i w_i f_k,i, with f_k,i formed as cn_scene_combine
+ *     forms it from the object planes d_obj_c [K][R*Nc] / d_obj_f [K][R*Nf]
+ *     (what went into cn_scene_combine) and the combined density; the products
+ *     rounded to float32, summed in float64 in a fixed order, rounded once.
+ *     The columns sum to d_out_acc up to rounding;
+ *   d_instance [R] int32: the lowest k with the largest d_obj_acc[r][k] when
+ *     d_out_acc[r] >= acc_min, else -1.
+ * d_obj_acc and d_instance may be NULL together; the object planes are then
+ * not read and may be NULL.  The three required outputs do not depend on that.
+ * Also refused: Nc < 1, Nf < 0, Nc + Nf > 256, zc_stride other than 0 or Nc,
+ * Nf > 0 with a NULL fine pointer, Nf == 0 with a fine pointer given, only one
+ * of d_obj_acc / d_instance, labels without d_obj_c (and d_obj_f when Nf > 0),
+ * acc_min NaN, R < 1 or R * (Nc + Nf) > CN_MAX_SAMPLES. */
+int cn_scene_composite(const float *d_sigma_c, const float *d_rgb_c, const float *d_z_c,
+                       int zc_stride, int Nc, const float *d_sigma_f, const float *d_rgb_f,
+                       const float *d_z_f, int Nf, const float *d_obj_c, const float *d_obj_f,
+                       const float *h_inv_s, int K, int R, int white_bg, float acc_min,
+                       float *d_out_rgb, float *d_out_depth, float *d_out_acc, float *d_obj_acc,
+                       int *d_instance, void *stream);
+
 /* ---- iso-surface of a density lattice (additive to ABI 4; no reference
  * counterpart): marching tetrahedra on the Kuhn (Freudenthal) triangulation,
  * which has no ambiguous case, and whose face diagonals agree between
