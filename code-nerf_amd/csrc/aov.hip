@@ -3,7 +3,7 @@
 // median depth and the weighted normal.
 //
 // Over a ray's samples k = 0 .. N-1 (the merged coarse + fine samples with
-// Nf > 0, by the rule of composite_fine_fwd_kernel) with the weights w_k that
+// Nf > 0, by the rule of merge_ray) with the weights w_k that
 // ray_forward leaves in RayState:
 //   depth_med = z_m for the first m with C_m >= 0.5, C_k = sum_{j <= k} (double)
 //               w_j in sample order; z_{N-1} when no such m exists;
@@ -13,19 +13,16 @@
 //               products rounded to fp32, summed in float64 in a fixed order
 //               and rounded once, as ray_reduce does.
 // One wave per ray, 4 rays per block, as the compositing kernels of render.hip,
-// whose ray_forward / ray_reduce run unchanged: rgb, depth and opacity are
+// with the same ray_forward / ray_reduce (cn_ray.h): rgb, depth and opacity are
 // cn_composite_fwd's / cn_composite_fine_fwd's bit for bit.  No atomics; every
 // output element is written by exactly one lane.
-#include "cn_common.h"
+#include "cn_ray.h"
 
 namespace cn {
 
 struct AovArgs {
-  const float *sig_c, *rgb_c, *zc;
-  int zc_stride, Nc;
+  MergePlanes p;                        // sig_f, rgb_f, zf NULL when Nf == 0
   const float* grad_c;                  // [R*Nc][3] or NULL
-  const float *sig_f, *rgb_f, *zf;      // NULL when Nf == 0
-  int Nf;
   const float* grad_f;                  // [R*Nf][3] or NULL
   int R, white_bg;
   float *out_rgb, *out_depth;           // required
@@ -44,24 +41,12 @@ CN_DEV void unit_normal(const float* g, float u[3]) {
   u[2] = ok ? -z / n : 0.f;
 }
 
-// inclusive prefix sum over lanes
-CN_DEV double wave_inclusive_sum(double v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int k = 1; k < 64; k <<= 1) {
-    const double o = shfl_up_d(v, k);
-    if (lane >= k) v += o;
-  }
-  return v;
-}
-
 template <bool kMerge>
 __global__ __launch_bounds__(256) void composite_aov_kernel(AovArgs a) {
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + wv;
   if (r >= a.R) return;                     // wave-uniform; only wave-level sync below
-  const int Nc = a.Nc, Nf = a.Nf;
-  const int N = Nc + Nf;
+  const int Nc = a.p.Nc, N = Nc + a.p.Nf;
   const bool nrm = a.out_normal != nullptr;
   RayState st;
   float u[kMaxPer][3];
@@ -69,47 +54,11 @@ __global__ __launch_bounds__(256) void composite_aov_kernel(AovArgs a) {
     // 4 waves x 256 slots x 9 floats = 36 KiB
     __shared__ float m_sig[4][kMaxRaySamples], m_z[4][kMaxRaySamples], m_rgb[4][kMaxRaySamples * 3];
     __shared__ float m_u[4][kMaxRaySamples * 3], z_stage[4][kMaxRaySamples];
-    const float* zcr = a.zc + (size_t)r * a.zc_stride;
-    const float* zfr = a.zf + (size_t)r * Nf;
-    auto wave_sync = [] {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-    float* zs = z_stage[wv];
-    for (int i = lane; i < Nc; i += 64) zs[i] = zcr[i];
-    for (int j = lane; j < Nf; j += 64) zs[Nc + j] = zfr[j];
-    wave_sync();
-    // merged position = own index + number of the other list's samples before
-    // it: with finite z always in [0, N); with non-finite z the ranks need not
-    // form a permutation, and an unwritten slot is only ever read, from LDS
-    for (int i = lane; i < Nc; i += 64) {
-      const float v = zs[i];
-      int lo = 0, hi = Nf;                  // count zf < v
-      while (lo < hi) { const int mid = (lo + hi) >> 1; if (zs[Nc + mid] < v) lo = mid + 1; else hi = mid; }
-      const int p = i + lo;
-      const size_t g = (size_t)r * Nc + i;
-      m_sig[wv][p] = a.sig_c[g];
-      m_z[wv][p] = v;
-      m_rgb[wv][3 * p + 0] = a.rgb_c[3 * g + 0];
-      m_rgb[wv][3 * p + 1] = a.rgb_c[3 * g + 1];
-      m_rgb[wv][3 * p + 2] = a.rgb_c[3 * g + 2];
-      if (nrm) unit_normal(a.grad_c + 3 * g, &m_u[wv][3 * p]);
-    }
-    for (int j = lane; j < Nf; j += 64) {
-      const float v = zs[Nc + j];
-      int lo = 0, hi = Nc;                  // count zc <= v
-      while (lo < hi) { const int mid = (lo + hi) >> 1; if (zs[mid] <= v) lo = mid + 1; else hi = mid; }
-      const int p = j + lo;
-      const size_t g = (size_t)r * Nf + j;
-      m_sig[wv][p] = a.sig_f[g];
-      m_z[wv][p] = v;
-      m_rgb[wv][3 * p + 0] = a.rgb_f[3 * g + 0];
-      m_rgb[wv][3 * p + 1] = a.rgb_f[3 * g + 1];
-      m_rgb[wv][3 * p + 2] = a.rgb_f[3 * g + 2];
-      if (nrm) unit_normal(a.grad_f + 3 * g, &m_u[wv][3 * p]);
-    }
-    wave_sync();
+    // no source table: the normals travel with their merged slot
+    merge_ray<false>(a.p, r, MergeRows{m_sig[wv], m_z[wv], m_rgb[wv], nullptr}, z_stage[wv],
+                     [&](int p, bool fine, size_t g) {
+                       if (nrm) unit_normal((fine ? a.grad_f : a.grad_c) + 3 * g, &m_u[wv][3 * p]);
+                     });
     ray_forward(st, m_sig[wv], m_rgb[wv], m_z[wv], N);
     if (nrm) {
 #pragma unroll
@@ -118,7 +67,7 @@ __global__ __launch_bounds__(256) void composite_aov_kernel(AovArgs a) {
           for (int c = 0; c < 3; ++c) u[k][c] = m_u[wv][3 * (st.n0 + k) + c];
     }
   } else {
-    ray_forward(st, a.sig_c + (size_t)r * Nc, a.rgb_c + (size_t)r * Nc * 3, a.zc + (size_t)r * a.zc_stride, Nc);
+    ray_forward(st, a.p.sig_c + (size_t)r * Nc, a.p.rgb_c + (size_t)r * Nc * 3, a.p.zc + (size_t)r * a.p.zc_stride, Nc);
     if (nrm) {
 #pragma unroll
       for (int k = 0; k < kMaxPer; ++k)
@@ -127,11 +76,7 @@ __global__ __launch_bounds__(256) void composite_aov_kernel(AovArgs a) {
   }
   float o[5];
   ray_reduce(st, o);
-  if (lane == 0) {
-    for (int c = 0; c < 3; ++c) a.out_rgb[3 * r + c] = a.white_bg ? fadd_rn(o[c] + 1.f, -o[4]) : o[c];
-    a.out_depth[r] = o[3];
-    if (a.out_acc) a.out_acc[r] = o[4];
-  }
+  store_ray(o, r, a.white_bg, a.out_rgb, a.out_depth, a.out_acc);
   if (a.out_med) {
     // C_k: the lanes own consecutive runs of samples, so the lane order is the
     // sample order -- prefix over the lanes, then along the lane's own run
@@ -167,9 +112,7 @@ __global__ __launch_bounds__(256) void composite_aov_kernel(AovArgs a) {
     }
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-      double v = acc[i];
-#pragma unroll
-      for (int k = 32; k > 0; k >>= 1) v += shfl_xor_d(v, k);
+      const double v = wave_sum(acc[i]);
       if (lane == 0) a.out_normal[3 * r + i] = (float)v;
     }
   }

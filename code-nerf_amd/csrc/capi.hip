@@ -560,19 +560,37 @@ int cn_composite_bwd(const float* d_sigma, const float* d_rgb, const float* d_z,
   return launch_check("composite_bwd_kernel");
 }
 
-int cn_render_loss(const float* d_sigma, const float* d_rgb, const float* d_z, int z_stride, int R, int N,
-                   int white_bg, const float* d_gt, int chunk, float* d_out_rgb, float* d_ray_se,
-                   float* d_chunk_loss, float* d_dsig, float* d_drgb, void* stream) {
-  if (!d_sigma || !d_rgb || !d_z || !d_gt || !d_out_rgb || !d_ray_se || !d_chunk_loss || !d_dsig || !d_drgb)
-    return fail("cn_render_loss: NULL argument");
-  if (check_rn(R, N, "cn_render_loss")) return -1;
-  if (chunk <= 0) return fail("cn_render_loss: chunk must be positive");
-  hipLaunchKernelGGL(render_loss_kernel, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), d_sigma, d_rgb, d_z,
-                     z_stride, R, N, white_bg, d_gt, chunk, d_out_rgb, d_ray_se, d_dsig, d_drgb);
-  if (launch_check("render_loss_kernel")) return -1;
+// The checks the four loss entries share, in the order every entry makes them.
+// A coarse entry passes Nf = 0; cn_render_loss, which takes any stride, z_stride = 0.
+static int check_loss(const char* who, bool fine, bool any_null, int R, int Nc, int Nf, int z_stride, int chunk) {
+  const std::string w(who);
+  const bool bad_stride = z_stride != 0 && z_stride != Nc;
+  if (any_null) return fail(w + ": NULL argument");
+  if (fine && (Nc <= 0 || Nf <= 0)) return fail(w + ": Nc and Nf must be positive");
+  if (check_rn(R, Nc + Nf, who)) return -1;
+  if (fine && bad_stride) return fail(w + ": zc_stride must be 0 or Nc");
+  if (chunk <= 0) return fail(w + ": chunk must be positive");
+  if (!fine && bad_stride) return fail(w + ": z_stride must be 0 or N");
+  return 0;
+}
+
+// the end of every loss entry: the ray kernel's launch status, then the chunk means
+static int finish_loss(const char* kernel, const float* d_ray_se, int R, int chunk, float* d_chunk_loss, void* stream) {
+  if (launch_check(kernel)) return -1;
   hipLaunchKernelGGL(chunk_loss_kernel, dim3(grid_for(R, chunk)), dim3(256), 0, S(stream), d_ray_se, R, chunk,
                      d_chunk_loss);
   return launch_check("chunk_loss_kernel");
+}
+
+int cn_render_loss(const float* d_sigma, const float* d_rgb, const float* d_z, int z_stride, int R, int N,
+                   int white_bg, const float* d_gt, int chunk, float* d_out_rgb, float* d_ray_se,
+                   float* d_chunk_loss, float* d_dsig, float* d_drgb, void* stream) {
+  const bool any_null =
+      !d_sigma || !d_rgb || !d_z || !d_gt || !d_out_rgb || !d_ray_se || !d_chunk_loss || !d_dsig || !d_drgb;
+  if (check_loss("cn_render_loss", false, any_null, R, N, 0, 0, chunk)) return -1;
+  hipLaunchKernelGGL(render_loss_kernel<false>, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), d_sigma, d_rgb, d_z,
+                     z_stride, R, N, white_bg, d_gt, chunk, d_out_rgb, d_ray_se, d_dsig, d_drgb, RayMask{});
+  return finish_loss("render_loss_kernel", d_ray_se, R, chunk, d_chunk_loss, stream);
 }
 
 // Host checks of the masked entries' extra arguments; *mk is what the kernel
@@ -590,19 +608,14 @@ int cn_render_loss_masked(const float* d_sigma, const float* d_rgb, const float*
                           int white_bg, const float* d_gt, int chunk, float* d_out_rgb, float* d_ray_se,
                           float* d_chunk_loss, float* d_dsig, float* d_drgb, const float* d_ray_weight,
                           const float* d_acc_target, float sil_coef, float* d_out_acc, void* stream) {
-  if (!d_sigma || !d_rgb || !d_z || !d_gt || !d_out_rgb || !d_ray_se || !d_chunk_loss || !d_dsig || !d_drgb)
-    return fail("cn_render_loss_masked: NULL argument");
-  if (check_rn(R, N, "cn_render_loss_masked")) return -1;
-  if (chunk <= 0) return fail("cn_render_loss_masked: chunk must be positive");
-  if (z_stride != 0 && z_stride != N) return fail("cn_render_loss_masked: z_stride must be 0 or N");
+  const bool any_null =
+      !d_sigma || !d_rgb || !d_z || !d_gt || !d_out_rgb || !d_ray_se || !d_chunk_loss || !d_dsig || !d_drgb;
+  if (check_loss("cn_render_loss_masked", false, any_null, R, N, 0, z_stride, chunk)) return -1;
   RayMask mk;
   if (check_mask(d_ray_weight, d_acc_target, sil_coef, d_out_acc, "cn_render_loss_masked", &mk)) return -1;
-  hipLaunchKernelGGL(render_loss_masked_kernel, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), d_sigma, d_rgb, d_z,
+  hipLaunchKernelGGL(render_loss_kernel<true>, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), d_sigma, d_rgb, d_z,
                      z_stride, R, N, white_bg, d_gt, chunk, d_out_rgb, d_ray_se, d_dsig, d_drgb, mk);
-  if (launch_check("render_loss_masked_kernel")) return -1;
-  hipLaunchKernelGGL(chunk_loss_kernel, dim3(grid_for(R, chunk)), dim3(256), 0, S(stream), d_ray_se, R, chunk,
-                     d_chunk_loss);
-  return launch_check("chunk_loss_kernel");
+  return finish_loss("render_loss_masked_kernel", d_ray_se, R, chunk, d_chunk_loss, stream);
 }
 
 int cn_sample_pdf(const float* d_sigma_c, const float* d_z_c, int zc_stride, int R, int Nc, const float* d_rand,
@@ -622,20 +635,13 @@ int cn_render_loss_fine(const float* d_sigma_c, const float* d_rgb_c, const floa
                         int white_bg, const float* d_gt, int chunk, float* d_out_rgb, float* d_ray_se,
                         float* d_chunk_loss, float* d_dsig_c, float* d_drgb_c, float* d_dsig_f, float* d_drgb_f,
                         void* stream) {
-  if (!d_sigma_c || !d_rgb_c || !d_z_c || !d_sigma_f || !d_rgb_f || !d_z_f || !d_gt || !d_out_rgb || !d_ray_se ||
-      !d_chunk_loss || !d_dsig_c || !d_drgb_c || !d_dsig_f || !d_drgb_f)
-    return fail("cn_render_loss_fine: NULL argument");
-  if (Nc <= 0 || Nf <= 0) return fail("cn_render_loss_fine: Nc and Nf must be positive");
-  if (check_rn(R, Nc + Nf, "cn_render_loss_fine")) return -1;
-  if (zc_stride != 0 && zc_stride != Nc) return fail("cn_render_loss_fine: zc_stride must be 0 or Nc");
-  if (chunk <= 0) return fail("cn_render_loss_fine: chunk must be positive");
-  hipLaunchKernelGGL(fine_render_loss_kernel, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), d_sigma_c, d_rgb_c,
-                     d_z_c, zc_stride, Nc, d_sigma_f, d_rgb_f, d_z_f, Nf, R, white_bg, d_gt, chunk, d_out_rgb,
-                     d_ray_se, d_dsig_c, d_drgb_c, d_dsig_f, d_drgb_f);
-  if (launch_check("fine_render_loss_kernel")) return -1;
-  hipLaunchKernelGGL(chunk_loss_kernel, dim3(grid_for(R, chunk)), dim3(256), 0, S(stream), d_ray_se, R, chunk,
-                     d_chunk_loss);
-  return launch_check("chunk_loss_kernel");
+  const bool any_null = !d_sigma_c || !d_rgb_c || !d_z_c || !d_sigma_f || !d_rgb_f || !d_z_f || !d_gt ||
+                        !d_out_rgb || !d_ray_se || !d_chunk_loss || !d_dsig_c || !d_drgb_c || !d_dsig_f || !d_drgb_f;
+  if (check_loss("cn_render_loss_fine", true, any_null, R, Nc, Nf, zc_stride, chunk)) return -1;
+  hipLaunchKernelGGL(fine_render_loss_kernel<false>, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), d_sigma_c,
+                     d_rgb_c, d_z_c, zc_stride, Nc, d_sigma_f, d_rgb_f, d_z_f, Nf, R, white_bg, d_gt, chunk, d_out_rgb,
+                     d_ray_se, d_dsig_c, d_drgb_c, d_dsig_f, d_drgb_f, RayMask{});
+  return finish_loss("fine_render_loss_kernel", d_ray_se, R, chunk, d_chunk_loss, stream);
 }
 
 int cn_render_loss_fine_masked(const float* d_sigma_c, const float* d_rgb_c, const float* d_z_c, int zc_stride, int Nc,
@@ -644,22 +650,15 @@ int cn_render_loss_fine_masked(const float* d_sigma_c, const float* d_rgb_c, con
                                float* d_chunk_loss, float* d_dsig_c, float* d_drgb_c, float* d_dsig_f,
                                float* d_drgb_f, const float* d_ray_weight, const float* d_acc_target, float sil_coef,
                                float* d_out_acc, void* stream) {
-  if (!d_sigma_c || !d_rgb_c || !d_z_c || !d_sigma_f || !d_rgb_f || !d_z_f || !d_gt || !d_out_rgb || !d_ray_se ||
-      !d_chunk_loss || !d_dsig_c || !d_drgb_c || !d_dsig_f || !d_drgb_f)
-    return fail("cn_render_loss_fine_masked: NULL argument");
-  if (Nc <= 0 || Nf <= 0) return fail("cn_render_loss_fine_masked: Nc and Nf must be positive");
-  if (check_rn(R, Nc + Nf, "cn_render_loss_fine_masked")) return -1;
-  if (zc_stride != 0 && zc_stride != Nc) return fail("cn_render_loss_fine_masked: zc_stride must be 0 or Nc");
-  if (chunk <= 0) return fail("cn_render_loss_fine_masked: chunk must be positive");
+  const bool any_null = !d_sigma_c || !d_rgb_c || !d_z_c || !d_sigma_f || !d_rgb_f || !d_z_f || !d_gt ||
+                        !d_out_rgb || !d_ray_se || !d_chunk_loss || !d_dsig_c || !d_drgb_c || !d_dsig_f || !d_drgb_f;
+  if (check_loss("cn_render_loss_fine_masked", true, any_null, R, Nc, Nf, zc_stride, chunk)) return -1;
   RayMask mk;
   if (check_mask(d_ray_weight, d_acc_target, sil_coef, d_out_acc, "cn_render_loss_fine_masked", &mk)) return -1;
-  hipLaunchKernelGGL(fine_render_loss_masked_kernel, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), d_sigma_c,
+  hipLaunchKernelGGL(fine_render_loss_kernel<true>, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), d_sigma_c,
                      d_rgb_c, d_z_c, zc_stride, Nc, d_sigma_f, d_rgb_f, d_z_f, Nf, R, white_bg, d_gt, chunk, d_out_rgb,
                      d_ray_se, d_dsig_c, d_drgb_c, d_dsig_f, d_drgb_f, mk);
-  if (launch_check("fine_render_loss_masked_kernel")) return -1;
-  hipLaunchKernelGGL(chunk_loss_kernel, dim3(grid_for(R, chunk)), dim3(256), 0, S(stream), d_ray_se, R, chunk,
-                     d_chunk_loss);
-  return launch_check("chunk_loss_kernel");
+  return finish_loss("fine_render_loss_masked_kernel", d_ray_se, R, chunk, d_chunk_loss, stream);
 }
 
 int cn_composite_fine_fwd(const float* d_sigma_c, const float* d_rgb_c, const float* d_z_c, int zc_stride, int Nc,
@@ -676,24 +675,30 @@ int cn_composite_fine_fwd(const float* d_sigma_c, const float* d_rgb_c, const fl
   return launch_check("composite_fine_fwd_kernel");
 }
 
+// The coarse + optional-fine argument rules of cn_composite_aov and
+// cn_scene_composite; extra_f is the entry's own fine-only pointer.
+static int check_coarse_fine(const char* who, const MergePlanes& p, const void* extra_f) {
+  const std::string w(who);
+  if (p.Nc < 1 || p.Nf < 0) return fail(w + ": Nc must be at least 1 and Nf at least 0");
+  if ((long long)p.Nc + p.Nf > 64 * kMaxPer) return fail(w + ": at most 256 samples per ray");
+  if (p.zc_stride != 0 && p.zc_stride != p.Nc) return fail(w + ": zc_stride must be 0 or Nc");
+  if (p.Nf > 0 && (!p.sig_f || !p.rgb_f || !p.zf)) return fail(w + ": Nf > 0 needs d_sigma_f, d_rgb_f and d_z_f");
+  if (p.Nf == 0 && (p.sig_f || p.rgb_f || p.zf || extra_f)) return fail(w + ": Nf == 0 takes no fine pointer");
+  return 0;
+}
+
 int cn_composite_aov(const float* d_sigma_c, const float* d_rgb_c, const float* d_z_c, int zc_stride, int Nc,
                      const float* d_grad_c, const float* d_sigma_f, const float* d_rgb_f, const float* d_z_f, int Nf,
                      const float* d_grad_f, int R, int white_bg, float* d_out_rgb, float* d_out_depth,
                      float* d_out_acc, float* d_out_depth_med, float* d_out_normal, void* stream) {
   if (!d_sigma_c || !d_rgb_c || !d_z_c || !d_out_rgb || !d_out_depth) return fail("cn_composite_aov: NULL argument");
-  if (Nc < 1 || Nf < 0) return fail("cn_composite_aov: Nc must be at least 1 and Nf at least 0");
-  if ((long long)Nc + Nf > 64 * kMaxPer) return fail("cn_composite_aov: at most 256 samples per ray");
-  if (zc_stride != 0 && zc_stride != Nc) return fail("cn_composite_aov: zc_stride must be 0 or Nc");
-  if (Nf > 0 && (!d_sigma_f || !d_rgb_f || !d_z_f))
-    return fail("cn_composite_aov: Nf > 0 needs d_sigma_f, d_rgb_f and d_z_f");
-  if (Nf == 0 && (d_sigma_f || d_rgb_f || d_z_f || d_grad_f))
-    return fail("cn_composite_aov: Nf == 0 takes no fine pointer");
+  const MergePlanes p{d_sigma_c, d_rgb_c, d_z_c, zc_stride, Nc, d_sigma_f, d_rgb_f, d_z_f, Nf};
+  if (check_coarse_fine("cn_composite_aov", p, d_grad_f)) return -1;
   if (d_out_normal && (!d_grad_c || (Nf > 0 && !d_grad_f)))
     return fail("cn_composite_aov: d_out_normal needs d_grad_c (and d_grad_f when Nf > 0)");
   if (!d_out_normal && (d_grad_c || d_grad_f)) return fail("cn_composite_aov: a gradient pointer needs d_out_normal");
   if (check_rn(R, Nc + Nf, "cn_composite_aov")) return -1;
-  const AovArgs a{d_sigma_c, d_rgb_c, d_z_c, zc_stride, Nc, d_grad_c, d_sigma_f, d_rgb_f, d_z_f, Nf, d_grad_f,
-                  R, white_bg, d_out_rgb, d_out_depth, d_out_acc, d_out_depth_med, d_out_normal};
+  const AovArgs a{p, d_grad_c, d_grad_f, R, white_bg, d_out_rgb, d_out_depth, d_out_acc, d_out_depth_med, d_out_normal};
   if (Nf > 0) hipLaunchKernelGGL(composite_aov_kernel<true>, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), a);
   else hipLaunchKernelGGL(composite_aov_kernel<false>, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), a);
   return launch_check("composite_aov_kernel");
@@ -753,13 +758,8 @@ int cn_scene_composite(const float* d_sigma_c, const float* d_rgb_c, const float
   if (!d_sigma_c || !d_rgb_c || !d_z_c || !h_inv_s || !d_out_rgb || !d_out_depth || !d_out_acc)
     return fail("cn_scene_composite: NULL argument");
   if (check_scene_k(K, "cn_scene_composite")) return -1;
-  if (Nc < 1 || Nf < 0) return fail("cn_scene_composite: Nc must be at least 1 and Nf at least 0");
-  if ((long long)Nc + Nf > 64 * kMaxPer) return fail("cn_scene_composite: at most 256 samples per ray");
-  if (zc_stride != 0 && zc_stride != Nc) return fail("cn_scene_composite: zc_stride must be 0 or Nc");
-  if (Nf > 0 && (!d_sigma_f || !d_rgb_f || !d_z_f))
-    return fail("cn_scene_composite: Nf > 0 needs d_sigma_f, d_rgb_f and d_z_f");
-  if (Nf == 0 && (d_sigma_f || d_rgb_f || d_z_f || d_obj_f))
-    return fail("cn_scene_composite: Nf == 0 takes no fine pointer");
+  const MergePlanes p{d_sigma_c, d_rgb_c, d_z_c, zc_stride, Nc, d_sigma_f, d_rgb_f, d_z_f, Nf};
+  if (check_coarse_fine("cn_scene_composite", p, d_obj_f)) return -1;
   if ((d_obj_acc == nullptr) != (d_instance == nullptr))
     return fail("cn_scene_composite: d_obj_acc and d_instance go together");
   if (d_obj_acc && (!d_obj_c || (Nf > 0 && !d_obj_f)))
@@ -771,8 +771,8 @@ int cn_scene_composite(const float* d_sigma_c, const float* d_rgb_c, const float
   }
   if (std::isnan(acc_min)) return fail("cn_scene_composite: acc_min is NaN");
   if (check_rn(R, Nc + Nf, "cn_scene_composite")) return -1;
-  const SceneCompositeArgs a{d_sigma_c, d_rgb_c, d_z_c, zc_stride, Nc, d_sigma_f, d_rgb_f, d_z_f, Nf, d_obj_c, d_obj_f,
-                             inv_s, K, R, white_bg, acc_min, d_out_rgb, d_out_depth, d_out_acc, d_obj_acc, d_instance};
+  const SceneCompositeArgs a{p, d_obj_c, d_obj_f, inv_s, K, R, white_bg, acc_min,
+                             d_out_rgb, d_out_depth, d_out_acc, d_obj_acc, d_instance};
   if (Nf > 0) hipLaunchKernelGGL(scene_composite_kernel<true>, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), a);
   else hipLaunchKernelGGL(scene_composite_kernel<false>, dim3(grid_for(R, 4)), dim3(256), 0, S(stream), a);
   return launch_check("scene_composite_kernel");

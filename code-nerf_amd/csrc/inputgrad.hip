@@ -33,6 +33,7 @@
 #pragma once
 #include "cn_common.h"
 #include "cn_layout.h"
+#include "cn_ray.h"
 
 namespace cn {
 
@@ -212,12 +213,6 @@ __global__ __launch_bounds__(kIgWaves * 64) void input_grad_kernel(InputGradArgs
   }
 }
 
-CN_DEV double ig_shfl_xor_d(double v, int k) {
-  const int lo = __shfl_xor(__double2loint(v), k);
-  const int hi = __shfl_xor(__double2hiint(v), k);
-  return __hiloint2double(hi, lo);
-}
-
 // Per-ray sums (mode B), one wave per ray like the compositing kernels:
 //   d_rays_o[r] = sum_s d_xyz,  d_rays_d[r] = sum_s (z_s d_xyz + d_viewdir)
 // lane l adds samples l, l + 64, ... in order, then a fixed xor butterfly; all
@@ -241,12 +236,10 @@ __global__ __launch_bounds__(256) void ray_grad_kernel(const float* __restrict__
     }
   }
 #pragma unroll
-  for (int k = 32; k > 0; k >>= 1)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      so[c] += ig_shfl_xor_d(so[c], k);
-      sd[c] += ig_shfl_xor_d(sd[c], k);
-    }
+  for (int c = 0; c < 3; ++c) {
+    so[c] = wave_sum(so[c]);
+    sd[c] = wave_sum(sd[c]);
+  }
   if (lane < 3) {
     dro[3 * (size_t)ray + lane] = (float)(lane == 0 ? so[0] : lane == 1 ? so[1] : so[2]);
     drd[3 * (size_t)ray + lane] = (float)(lane == 0 ? sd[0] : lane == 1 ? sd[1] : sd[2]);

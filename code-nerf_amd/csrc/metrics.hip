@@ -26,9 +26,7 @@
 // Every block sum is a fixed xor butterfly per wave and a fixed order over the
 // waves: no atomics, deterministic, and a view's numbers depend on its own
 // blocks only (not on V or on the views beside it).
-//
-// Included by capi.hip after render.hip (shfl_xor_d).
-#include "cn_common.h"
+#include "cn_ray.h"
 
 namespace cn {
 
@@ -62,8 +60,7 @@ inline MetricsGeom metrics_geom(int H, int W, int chunk) {
 // Sum over the 256 threads of a block, the same value in every thread of wave
 // 0 .. 3 after the call; `red` is 4 doubles of LDS.
 CN_DEV double metrics_block_sum(double s, double* red) {
-#pragma unroll
-  for (int k = 32; k > 0; k >>= 1) s += shfl_xor_d(s, k);
+  s = wave_sum(s);
   __syncthreads();                       // red may still be read from an earlier sum
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();

@@ -4,15 +4,13 @@
 //   composite fwd/bwd   reference src/utils.py:34-47 and its autograd
 //   render_loss         composite + chunk-mean MSE (src/trainer.py:75) + the
 //                       composite backward, fused per ray for training
-//   render_loss_masked  the same with a weight per ray and a silhouette term
+//   render_loss<true>   the same with a weight per ray and a silhouette term
 //                       on the ray's accumulated opacity (no reference
 //                       counterpart in code)
 //
-// One wave per ray: lane l owns a contiguous run of samples, the exclusive
-// transmittance product and the reverse cumulative sum are wave scans.  Both
-// accumulate in float64, as torch's CPU cumprod/cumsum do (acc_type<float> is
-// double on the CPU), so the rounded float results match the reference.
-#include "cn_common.h"
+// The ray itself (one wave per ray: ray_forward, ray_reduce, ray_backward and
+// the coarse + fine merge_ray) is cn_ray.h.
+#include "cn_ray.h"
 
 namespace cn {
 
@@ -64,10 +62,6 @@ __global__ __launch_bounds__(256) void get_rays_kernel(int H, int W, double foca
 // the partials in a fixed order.  Written, not accumulated; deterministic.
 constexpr int kRaysBwdBlock = 256;
 
-CN_DEV double shfl_xor_d(double v, int k) {
-  return __hiloint2double(__shfl_xor(__double2hiint(v), k), __shfl_xor(__double2loint(v), k));
-}
-
 __global__ __launch_bounds__(kRaysBwdBlock) void get_rays_bwd_partial_kernel(
     int H, int W, double focal, int focal_f64, const float* __restrict__ c2w, const float* __restrict__ dro,
     const float* __restrict__ dvd, double* __restrict__ part) {
@@ -115,9 +109,7 @@ __global__ __launch_bounds__(kRaysBwdBlock) void get_rays_bwd_partial_kernel(
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
   for (int i = 0; i < 12; ++i) {
-    double s = t[i];
-#pragma unroll
-    for (int k = 32; k > 0; k >>= 1) s += shfl_xor_d(s, k);
+    const double s = wave_sum(t[i]);
     if (lane == 0) red[w][i] = s;
   }
   __syncthreads();
@@ -136,8 +128,7 @@ __global__ __launch_bounds__(kRaysBwdBlock) void get_rays_bwd_final_kernel(const
   for (int i = 0; i < 12; ++i) {
     double s = 0.0;
     for (int b = threadIdx.x; b < nblocks; b += kRaysBwdBlock) s += part[(size_t)b * 12 + i];
-#pragma unroll
-    for (int k = 32; k > 0; k >>= 1) s += shfl_xor_d(s, k);
+    s = wave_sum(s);
     if (lane == 0) red[w] = s;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -147,156 +138,6 @@ __global__ __launch_bounds__(kRaysBwdBlock) void get_rays_bwd_final_kernel(const
       dc2w[i] = (float)tot;
     }
     __syncthreads();
-  }
-}
-
-// ---------------------------------------------------------------- scans
-CN_DEV double shfl_up_d(double v, int k) {
-  const int lo = __shfl_up(__double2loint(v), k);
-  const int hi = __shfl_up(__double2hiint(v), k);
-  return __hiloint2double(hi, lo);
-}
-CN_DEV double shfl_down_d(double v, int k) {
-  const int lo = __shfl_down(__double2loint(v), k);
-  const int hi = __shfl_down(__double2hiint(v), k);
-  return __hiloint2double(hi, lo);
-}
-// exclusive product over lanes (lane 0 gets 1)
-CN_DEV double wave_exclusive_prod(double v) {
-  const int lane = threadIdx.x & 63;
-  double incl = v;
-#pragma unroll
-  for (int k = 1; k < 64; k <<= 1) {
-    const double o = shfl_up_d(incl, k);
-    if (lane >= k) incl *= o;
-  }
-  double ex = shfl_up_d(incl, 1);
-  return lane == 0 ? 1.0 : ex;
-}
-// exclusive suffix sum over lanes (lane 63 gets 0)
-CN_DEV double wave_exclusive_suffix_sum(double v) {
-  const int lane = threadIdx.x & 63;
-  double incl = v;
-#pragma unroll
-  for (int k = 1; k < 64; k <<= 1) {
-    const double o = shfl_down_d(incl, k);
-    if (lane + k < 64) incl += o;
-  }
-  double ex = shfl_down_d(incl, 1);
-  return lane == 63 ? 0.0 : ex;
-}
-CN_DEV float wave_sum(float v) {
-#pragma unroll
-  for (int k = 32; k > 0; k >>= 1) v += __shfl_xor(v, k);
-  return v;
-}
-
-constexpr int kMaxPer = 4;   // samples per lane: N <= 256
-
-struct RayState {
-  int n0, cnt;                // this lane's sample range
-  float sig[kMaxPer], z[kMaxPer], delta[kMaxPer], e[kMaxPer], alpha[kMaxPer], trans[kMaxPer];
-  float T[kMaxPer], w[kMaxPer], c[kMaxPer][3];
-};
-
-// Forward of one ray (src/utils.py:35-43), lane-local part + scan.
-CN_DEV void ray_forward(RayState& st, const float* sig, const float* rgb, const float* z, int N) {
-  const int lane = threadIdx.x & 63;
-  const int per = (N + 63) / 64;
-  st.n0 = lane * per;
-  st.cnt = max(0, min(per, N - st.n0));
-  double prod = 1.0;
-#pragma unroll
-  for (int k = 0; k < kMaxPer; ++k) {
-    if (k < st.cnt) {
-      const int s = st.n0 + k;
-      st.sig[k] = sig[s];
-      st.z[k] = z[s];
-      st.delta[k] = s + 1 < N ? fadd_rn(z[s + 1], -z[s]) : 1e10f;
-      st.e[k] = expf(-fmul_rn(st.sig[k], st.delta[k]));
-      st.alpha[k] = 1.f - st.e[k];
-      st.trans[k] = fadd_rn(1.f - st.alpha[k], 1e-10f);
-      if (rgb) {
-        st.c[k][0] = rgb[3 * s + 0];
-        st.c[k][1] = rgb[3 * s + 1];
-        st.c[k][2] = rgb[3 * s + 2];
-      }
-      prod *= (double)st.trans[k];
-    }
-  }
-  double run = wave_exclusive_prod(prod);
-#pragma unroll
-  for (int k = 0; k < kMaxPer; ++k) {
-    if (k < st.cnt) {
-      st.T[k] = (float)run;
-      run *= (double)st.trans[k];
-      st.w[k] = fmul_rn(st.alpha[k], st.T[k]);
-    }
-  }
-}
-
-// rgb (3), depth, weight sum of a ray (sums in float64, rounded once)
-CN_DEV void ray_reduce(const RayState& st, float out[5]) {
-  double acc[5] = {0, 0, 0, 0, 0};
-#pragma unroll
-  for (int k = 0; k < kMaxPer; ++k) {
-    if (k < st.cnt) {
-      acc[0] += (double)fmul_rn(st.w[k], st.c[k][0]);
-      acc[1] += (double)fmul_rn(st.w[k], st.c[k][1]);
-      acc[2] += (double)fmul_rn(st.w[k], st.c[k][2]);
-      acc[3] += (double)fmul_rn(st.w[k], st.z[k]);
-      acc[4] += (double)st.w[k];
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 5; ++i) {
-    double v = acc[i];
-#pragma unroll
-    for (int k = 32; k > 0; k >>= 1) v += __hiloint2double(__shfl_xor(__double2hiint(v), k),
-                                                           __shfl_xor(__double2loint(v), k));
-    out[i] = (float)v;
-  }
-}
-
-// Backward of one ray given d rgb_final (3) and d depth, as torch autograd.
-// kAcc: g_acc, the gradient of the ray's weight sum (the silhouette term of
-// the masked losses), is added to every sample's d weight as well; without it
-// the sums are exactly the three below.
-template <bool kAcc = false>
-CN_DEV void ray_backward(const RayState& st, const float g[3], float gd, int white_bg,
-                         float* dsig, float* drgb, float g_acc = 0.f) {
-  const float gw_bg = white_bg ? -(g[0] + g[1] + g[2]) : 0.f;
-  float dw[kMaxPer], wdT[kMaxPer];
-  double part = 0.0;
-#pragma unroll
-  for (int k = 0; k < kMaxPer; ++k) {
-    if (k < st.cnt) {
-      // d weights = sum_c g_c c_c  + d(wsum) + gd * z
-      float v = fadd_rn(fadd_rn(fmul_rn(g[0], st.c[k][0]), fmul_rn(g[1], st.c[k][1])), fmul_rn(g[2], st.c[k][2]));
-      v = fadd_rn(v, gw_bg);
-      if constexpr (kAcc) v = fadd_rn(v, g_acc);
-      v = fadd_rn(v, fmul_rn(gd, st.z[k]));
-      dw[k] = v;
-      // grad of cumprod output T_k is dw_k * alpha_k; reversed cumsum of T_k * dT_k
-      wdT[k] = fmul_rn(st.T[k], fmul_rn(v, st.alpha[k]));
-      part += (double)wdT[k];
-    }
-  }
-  // suffix sums strictly after each sample: across lanes, then within the lane
-  double after = wave_exclusive_suffix_sum(part);
-#pragma unroll
-  for (int k = kMaxPer - 1; k >= 0; --k) {
-    if (k < st.cnt) {
-      const int s = st.n0 + k;
-      // d trans_k = (sum_{j > k} T_j dT_j) / trans_k
-      const float dtrans = (float)after / st.trans[k];
-      after += (double)wdT[k];
-      const float dalpha = fadd_rn(fmul_rn(dw[k], st.T[k]), -dtrans);
-      dsig[s] = fmul_rn(fmul_rn(dalpha, st.e[k]), st.delta[k]);
-      drgb[3 * s + 0] = fmul_rn(st.w[k], g[0]);
-      drgb[3 * s + 1] = fmul_rn(st.w[k], g[1]);
-      drgb[3 * s + 2] = fmul_rn(st.w[k], g[2]);
-    }
   }
 }
 
@@ -311,12 +152,12 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(const float* __restr
   ray_forward(st, sig + (size_t)r * N, rgb + (size_t)r * N * 3, z + (size_t)r * z_stride, N);
   float o[5];
   ray_reduce(st, o);
-  if ((threadIdx.x & 63) == 0) {
-    for (int c = 0; c < 3; ++c) out_rgb[3 * r + c] = white_bg ? fadd_rn(o[c] + 1.f, -o[4]) : o[c];
-    out_depth[r] = o[3];
+  store_ray(o, r, white_bg, out_rgb, out_depth, nullptr);
+  if (out_w) {
+#pragma unroll
+    for (int k = 0; k < kMaxPer; ++k)
+      if (k < st.cnt) out_w[(size_t)r * N + st.n0 + k] = st.w[k];
   }
-  if (out_w)
-    for (int k = 0; k < st.cnt; ++k) out_w[(size_t)r * N + st.n0 + k] = st.w[k];
 }
 
 __global__ __launch_bounds__(256) void composite_bwd_kernel(const float* __restrict__ sig, const float* __restrict__ rgb,
@@ -333,7 +174,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const float* __restr
   ray_backward(st, g, gd, white_bg, dsig + (size_t)r * N, drgb + (size_t)r * N * 3);
 }
 
-// The masked variant of both loss kernels: a weight m_r >= 0 per ray (NULL:
+// The kMasked instantiation of both loss kernels: a weight m_r >= 0 per ray (NULL:
 // 1), and with sil_coef > 0 a target a_r for the ray's accumulated opacity
 // acc_r = sum_k w_k (ray_reduce's o[4]; the fine kernel's runs over the merged
 // samples).  Per chunk of nb rays
@@ -341,8 +182,9 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const float* __restr
 // so ray_se[r] = m_r se_r + 3 sil_coef (acc_r - a_r)^2 goes through
 // chunk_loss_kernel unchanged, d col_c = m_r (2 / (3 nb)) diff_c, and
 // d acc = sil_coef (2 / nb) (acc_r - a_r) joins every sample's d weight in
-// ray_backward.  m = 1 and sil_coef = 0 give the plain kernels' bits.  The
-// host passes sil_coef = 0 when acc_target is NULL.
+// ray_backward.  m = 1 and sil_coef = 0 give the plain kernels' bits: every
+// other operation is ray_loss's, shared with them.  The host passes
+// sil_coef = 0 when acc_target is NULL.
 struct RayMask {
   const float* weight;       // [R] or NULL
   const float* acc_target;   // [R]; read only when sil_coef > 0
@@ -365,71 +207,54 @@ CN_DEV float masked_ray_loss(const RayMask& mk, int r, int nb, float se, float a
   return out;
 }
 
-// Training: composite, per-ray squared error, d rgb of the chunk-mean MSE
-// (chunk = `chunk` consecutive rays, src/trainer.py:69,75), composite backward.
-__global__ __launch_bounds__(256) void render_loss_kernel(const float* __restrict__ sig, const float* __restrict__ rgb,
-                                                          const float* __restrict__ z, int z_stride, int R, int N,
-                                                          int white_bg, const float* __restrict__ gt, int chunk,
-                                                          float* __restrict__ out_rgb, float* __restrict__ ray_se,
-                                                          float* __restrict__ dsig, float* __restrict__ drgb) {
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= R) return;
-  RayState st;
-  ray_forward(st, sig + (size_t)r * N, rgb + (size_t)r * N * 3, z + (size_t)r * z_stride, N);
-  float o[5];
-  ray_reduce(st, o);
-  float col[3], g[3];
+// The loss body of the four loss kernels, from ray_reduce's sums o of ray r:
+// the ray's colour, its squared error and g = d loss / d colour of the
+// chunk-mean MSE (chunk = `chunk` consecutive rays, src/trainer.py:69,75);
+// lane 0 stores out_rgb and ray_se.  kMasked adds the loss of RayMask
+// (masked_ray_loss) and the opacity output; the plain instantiation does not
+// read mk.  -> d loss / d opacity (0 when not masked), for ray_backward.
+template <bool kMasked>
+CN_DEV float ray_loss(const float o[5], int r, int R, int white_bg, const float* gt, int chunk, float* out_rgb,
+                      float* ray_se, const RayMask& mk, float g[3]) {
+  float col[3];
   const int c0 = (r / chunk) * chunk;
   const int nb = min(chunk, R - c0);
   const float inv = 1.f / (float)(3 * nb);
   float se = 0.f;
   for (int c = 0; c < 3; ++c) {
-    col[c] = white_bg ? fadd_rn(o[c] + 1.f, -o[4]) : o[c];
-    const float diff = col[c] - gt[3 * r + c];
-    se += diff * diff;
-    // d mean(diff^2) = 2 * diff / numel
-    g[c] = fmul_rn(fmul_rn(inv, 2.f), diff);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    for (int c = 0; c < 3; ++c) out_rgb[3 * r + c] = col[c];
-    ray_se[r] = se;
-  }
-  ray_backward(st, g, 0.f, white_bg, dsig + (size_t)r * N, drgb + (size_t)r * N * 3);
-}
-
-// The same with the loss of RayMask (masked_ray_loss): the plain kernel's body
-// plus the weight, the silhouette term and the opacity output.
-__global__ __launch_bounds__(256) void render_loss_masked_kernel(const float* __restrict__ sig, const float* __restrict__ rgb,
-                             const float* __restrict__ z, int z_stride, int R, int N, int white_bg,
-                             const float* __restrict__ gt, int chunk, float* __restrict__ out_rgb,
-                             float* __restrict__ ray_se, float* __restrict__ dsig, float* __restrict__ drgb,
-                             RayMask mk) {
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= R) return;
-  RayState st;
-  ray_forward(st, sig + (size_t)r * N, rgb + (size_t)r * N * 3, z + (size_t)r * z_stride, N);
-  float o[5];
-  ray_reduce(st, o);
-  float col[3], g[3];
-  const int c0 = (r / chunk) * chunk;
-  const int nb = min(chunk, R - c0);
-  const float inv = 1.f / (float)(3 * nb);
-  float se = 0.f;
-  for (int c = 0; c < 3; ++c) {
-    col[c] = white_bg ? fadd_rn(o[c] + 1.f, -o[4]) : o[c];
+    col[c] = ray_colour(o, c, white_bg);
     const float diff = col[c] - gt[3 * r + c];
     se += diff * diff;
     // d mean(diff^2) = 2 * diff / numel
     g[c] = fmul_rn(fmul_rn(inv, 2.f), diff);
   }
   float g_acc = 0.f;
-  se = masked_ray_loss(mk, r, nb, se, o[4], g, &g_acc);
+  if constexpr (kMasked) se = masked_ray_loss(mk, r, nb, se, o[4], g, &g_acc);
   if ((threadIdx.x & 63) == 0) {
     for (int c = 0; c < 3; ++c) out_rgb[3 * r + c] = col[c];
     ray_se[r] = se;
-    if (mk.out_acc) mk.out_acc[r] = o[4];
+    if constexpr (kMasked)
+      if (mk.out_acc) mk.out_acc[r] = o[4];
   }
-  ray_backward<true>(st, g, 0.f, white_bg, dsig + (size_t)r * N, drgb + (size_t)r * N * 3, g_acc);
+  return g_acc;
+}
+
+// Training: composite, the loss (ray_loss), composite backward.
+template <bool kMasked>
+__global__ __launch_bounds__(256) void render_loss_kernel(const float* __restrict__ sig, const float* __restrict__ rgb,
+                                                          const float* __restrict__ z, int z_stride, int R, int N,
+                                                          int white_bg, const float* __restrict__ gt, int chunk,
+                                                          float* __restrict__ out_rgb, float* __restrict__ ray_se,
+                                                          float* __restrict__ dsig, float* __restrict__ drgb,
+                                                          RayMask mk) {
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= R) return;
+  RayState st;
+  ray_forward(st, sig + (size_t)r * N, rgb + (size_t)r * N * 3, z + (size_t)r * z_stride, N);
+  float o[5], g[3];
+  ray_reduce(st, o);
+  const float g_acc = ray_loss<kMasked>(o, r, R, white_bg, gt, chunk, out_rgb, ray_se, mk, g);
+  ray_backward<kMasked>(st, g, 0.f, white_bg, dsig + (size_t)r * N, drgb + (size_t)r * N * 3, g_acc);
 }
 
 // chunk-mean MSE values from per-ray squared errors (one block per chunk)
@@ -459,8 +284,6 @@ __global__ __launch_bounds__(256) void chunk_loss_kernel(const float* __restrict
 // pdf = (w[1:-1] + 1e-5) / sum, cdf = [0, cumsum] (float64, rounded once),
 // u_j = (j + rnd_j) / Nf (stratified, so z_f comes out sorted), z_f = inverse
 // cdf with NeRF's degenerate-bin rule (denom < 1e-5 -> 1).
-constexpr int kMaxRaySamples = 64 * kMaxPer;
-
 __global__ __launch_bounds__(256) void sample_pdf_kernel(const float* __restrict__ sig, const float* __restrict__ z,
                                                          int z_stride, int R, int Nc,
                                                          const float* __restrict__ rnd, int Nf,
@@ -484,16 +307,9 @@ __global__ __launch_bounds__(256) void sample_pdf_kernel(const float* __restrict
       part += (double)wv_[k];
     }
   }
-  // exclusive prefix over lanes
-  double incl = part;
-#pragma unroll
-  for (int k = 1; k < 64; k <<= 1) {
-    const double o = shfl_up_d(incl, k);
-    if (lane >= k) incl += o;
-  }
-  double total = incl;
-  total = __hiloint2double(__shfl(__double2hiint(total), 63), __shfl(__double2loint(total), 63));
-  double run = incl - part;
+  const double incl = wave_inclusive_sum(part);
+  const double total = __hiloint2double(__shfl(__double2hiint(incl), 63), __shfl(__double2loint(incl), 63));
+  double run = incl - part;             // exclusive prefix over lanes
   float* cdf = cdf_s[wv];
   float* bins = bin_s[wv];
 #pragma unroll
@@ -507,10 +323,8 @@ __global__ __launch_bounds__(256) void sample_pdf_kernel(const float* __restrict
       if (s + 1 < Nc) bins[s] = fmul_rn(0.5f, fadd_rn(zr[s], zr[s + 1]));
     }
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  const int nb = Nc - 1;                    // cdf / bin entries
+  wave_sync();
+  const int nb = Nc - 1;                   // cdf / bin entries
   for (int j = lane; j < Nf; j += 64) {
     const float u = (float)j + rnd[(size_t)r * Nf + j];
     const float uu = u / (float)Nf;
@@ -530,109 +344,12 @@ __global__ __launch_bounds__(256) void sample_pdf_kernel(const float* __restrict
   }
 }
 
-// Fine composite + chunk-mean MSE + backward over the union of the coarse
-// and fine samples of each ray (merged by z; a coarse sample precedes a fine
-// one at equal z).  dsig_c / drgb_c are ACCUMULATED into (they already hold
-// the coarse loss's gradient); dsig_f / drgb_f are written.
+// Fine composite + the loss (ray_loss) + backward over the union of the coarse
+// and fine samples of each ray (merge_ray).  dsig_c / drgb_c are ACCUMULATED
+// into (they already hold the coarse loss's gradient); dsig_f / drgb_f are
+// written.  With kMasked the opacity runs over the merged samples.
+template <bool kMasked>
 __global__ __launch_bounds__(256) void fine_render_loss_kernel(
-    const float* __restrict__ sig_c, const float* __restrict__ rgb_c, const float* __restrict__ zc, int zc_stride,
-    int Nc, const float* __restrict__ sig_f, const float* __restrict__ rgb_f, const float* __restrict__ zf, int Nf,
-    int R, int white_bg, const float* __restrict__ gt, int chunk, float* __restrict__ out_rgb,
-    float* __restrict__ ray_se, float* __restrict__ dsig_c, float* __restrict__ drgb_c,
-    float* __restrict__ dsig_f, float* __restrict__ drgb_f) {
-  __shared__ float m_sig[4][kMaxRaySamples], m_z[4][kMaxRaySamples], m_rgb[4][kMaxRaySamples * 3];
-  __shared__ float m_dsig[4][kMaxRaySamples], m_drgb[4][kMaxRaySamples * 3];
-  __shared__ int m_src[4][kMaxRaySamples];
-  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int r = blockIdx.x * 4 + wv;
-  if (r >= R) return;                       // wave-uniform; only wave-level sync below
-  const int N = Nc + Nf;
-  const float* zcr = zc + (size_t)r * zc_stride;
-  const float* zfr = zf + (size_t)r * Nf;
-  auto wave_sync = [] {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  };
-  // Every merged slot starts as "no source": with non-finite z (diverged
-  // weights) the two rank computations below need not form a permutation, and
-  // an unwritten slot must not scatter through an undefined index.
-  for (int p = lane; p < N; p += 64) m_src[wv][p] = -1;
-  // the ray's coarse and fine z staged in LDS (m_dsig is written only by the
-  // backward below): the rank searches' dependent reads then cost LDS, not
-  // global-memory, latency
-  float* zs = m_dsig[wv];
-  for (int i = lane; i < Nc; i += 64) zs[i] = zcr[i];
-  for (int j = lane; j < Nf; j += 64) zs[Nc + j] = zfr[j];
-  wave_sync();
-  // merged position = own index + number of the other list's samples before it
-  for (int i = lane; i < Nc; i += 64) {
-    const float v = zs[i];
-    int lo = 0, hi = Nf;                    // count zf < v
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (zs[Nc + mid] < v) lo = mid + 1; else hi = mid; }
-    const int p = i + lo;
-    const size_t g = (size_t)r * Nc + i;
-    m_sig[wv][p] = sig_c[g];
-    m_z[wv][p] = v;
-    m_rgb[wv][3 * p + 0] = rgb_c[3 * g + 0];
-    m_rgb[wv][3 * p + 1] = rgb_c[3 * g + 1];
-    m_rgb[wv][3 * p + 2] = rgb_c[3 * g + 2];
-    m_src[wv][p] = i;
-  }
-  for (int j = lane; j < Nf; j += 64) {
-    const float v = zs[Nc + j];
-    int lo = 0, hi = Nc;                    // count zc <= v
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (zs[mid] <= v) lo = mid + 1; else hi = mid; }
-    const int p = j + lo;
-    const size_t g = (size_t)r * Nf + j;
-    m_sig[wv][p] = sig_f[g];
-    m_z[wv][p] = v;
-    m_rgb[wv][3 * p + 0] = rgb_f[3 * g + 0];
-    m_rgb[wv][3 * p + 1] = rgb_f[3 * g + 1];
-    m_rgb[wv][3 * p + 2] = rgb_f[3 * g + 2];
-    m_src[wv][p] = Nc + j;
-  }
-  wave_sync();
-  RayState st;
-  ray_forward(st, m_sig[wv], m_rgb[wv], m_z[wv], N);
-  float o[5];
-  ray_reduce(st, o);
-  float col[3], gr[3];
-  const int c0 = (r / chunk) * chunk;
-  const int nbr = min(chunk, R - c0);
-  const float inv = 1.f / (float)(3 * nbr);
-  float se = 0.f;
-  for (int c = 0; c < 3; ++c) {
-    col[c] = white_bg ? fadd_rn(o[c] + 1.f, -o[4]) : o[c];
-    const float diff = col[c] - gt[3 * r + c];
-    se += diff * diff;
-    gr[c] = fmul_rn(fmul_rn(inv, 2.f), diff);
-  }
-  if (lane == 0) {
-    for (int c = 0; c < 3; ++c) out_rgb[3 * r + c] = col[c];
-    ray_se[r] = se;
-  }
-  ray_backward(st, gr, 0.f, white_bg, m_dsig[wv], m_drgb[wv]);
-  wave_sync();
-  for (int p = lane; p < N; p += 64) {
-    const int src = m_src[wv][p];
-    if (src < 0) continue;
-    if (src < Nc) {
-      const size_t g = (size_t)r * Nc + src;
-      dsig_c[g] += m_dsig[wv][p];
-      for (int c = 0; c < 3; ++c) drgb_c[3 * g + c] += m_drgb[wv][3 * p + c];
-    } else {
-      const size_t g = (size_t)r * Nf + (src - Nc);
-      dsig_f[g] = m_dsig[wv][p];
-      for (int c = 0; c < 3; ++c) drgb_f[3 * g + c] = m_drgb[wv][3 * p + c];
-    }
-  }
-}
-
-// fine_render_loss_kernel with the loss of RayMask (the opacity over the merged
-// samples): the plain kernel's body plus the weight, the silhouette term and
-// the opacity output.
-__global__ __launch_bounds__(256) void fine_render_loss_masked_kernel(
     const float* __restrict__ sig_c, const float* __restrict__ rgb_c, const float* __restrict__ zc, int zc_stride,
     int Nc, const float* __restrict__ sig_f, const float* __restrict__ rgb_f, const float* __restrict__ zf, int Nf,
     int R, int white_bg, const float* __restrict__ gt, int chunk, float* __restrict__ out_rgb,
@@ -645,75 +362,15 @@ __global__ __launch_bounds__(256) void fine_render_loss_masked_kernel(
   const int r = blockIdx.x * 4 + wv;
   if (r >= R) return;                       // wave-uniform; only wave-level sync below
   const int N = Nc + Nf;
-  const float* zcr = zc + (size_t)r * zc_stride;
-  const float* zfr = zf + (size_t)r * Nf;
-  auto wave_sync = [] {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  };
-  // Every merged slot starts as "no source": with non-finite z (diverged
-  // weights) the two rank computations below need not form a permutation, and
-  // an unwritten slot must not scatter through an undefined index.
-  for (int p = lane; p < N; p += 64) m_src[wv][p] = -1;
-  // the ray's coarse and fine z staged in LDS (m_dsig is written only by the
-  // backward below): the rank searches' dependent reads then cost LDS, not
-  // global-memory, latency
-  float* zs = m_dsig[wv];
-  for (int i = lane; i < Nc; i += 64) zs[i] = zcr[i];
-  for (int j = lane; j < Nf; j += 64) zs[Nc + j] = zfr[j];
-  wave_sync();
-  // merged position = own index + number of the other list's samples before it
-  for (int i = lane; i < Nc; i += 64) {
-    const float v = zs[i];
-    int lo = 0, hi = Nf;                    // count zf < v
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (zs[Nc + mid] < v) lo = mid + 1; else hi = mid; }
-    const int p = i + lo;
-    const size_t g = (size_t)r * Nc + i;
-    m_sig[wv][p] = sig_c[g];
-    m_z[wv][p] = v;
-    m_rgb[wv][3 * p + 0] = rgb_c[3 * g + 0];
-    m_rgb[wv][3 * p + 1] = rgb_c[3 * g + 1];
-    m_rgb[wv][3 * p + 2] = rgb_c[3 * g + 2];
-    m_src[wv][p] = i;
-  }
-  for (int j = lane; j < Nf; j += 64) {
-    const float v = zs[Nc + j];
-    int lo = 0, hi = Nc;                    // count zc <= v
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (zs[mid] <= v) lo = mid + 1; else hi = mid; }
-    const int p = j + lo;
-    const size_t g = (size_t)r * Nf + j;
-    m_sig[wv][p] = sig_f[g];
-    m_z[wv][p] = v;
-    m_rgb[wv][3 * p + 0] = rgb_f[3 * g + 0];
-    m_rgb[wv][3 * p + 1] = rgb_f[3 * g + 1];
-    m_rgb[wv][3 * p + 2] = rgb_f[3 * g + 2];
-    m_src[wv][p] = Nc + j;
-  }
-  wave_sync();
+  // the gradients scatter through m_src; m_dsig stages z until the backward
+  merge_ray<true>(MergePlanes{sig_c, rgb_c, zc, zc_stride, Nc, sig_f, rgb_f, zf, Nf}, r,
+                  MergeRows{m_sig[wv], m_z[wv], m_rgb[wv], m_src[wv]}, m_dsig[wv]);
   RayState st;
   ray_forward(st, m_sig[wv], m_rgb[wv], m_z[wv], N);
-  float o[5];
+  float o[5], g[3];
   ray_reduce(st, o);
-  float col[3], gr[3];
-  const int c0 = (r / chunk) * chunk;
-  const int nbr = min(chunk, R - c0);
-  const float inv = 1.f / (float)(3 * nbr);
-  float se = 0.f;
-  for (int c = 0; c < 3; ++c) {
-    col[c] = white_bg ? fadd_rn(o[c] + 1.f, -o[4]) : o[c];
-    const float diff = col[c] - gt[3 * r + c];
-    se += diff * diff;
-    gr[c] = fmul_rn(fmul_rn(inv, 2.f), diff);
-  }
-  float g_acc = 0.f;
-  se = masked_ray_loss(mk, r, nbr, se, o[4], gr, &g_acc);
-  if (lane == 0) {
-    for (int c = 0; c < 3; ++c) out_rgb[3 * r + c] = col[c];
-    ray_se[r] = se;
-    if (mk.out_acc) mk.out_acc[r] = o[4];
-  }
-  ray_backward<true>(st, gr, 0.f, white_bg, m_dsig[wv], m_drgb[wv], g_acc);
+  const float g_acc = ray_loss<kMasked>(o, r, R, white_bg, gt, chunk, out_rgb, ray_se, mk, g);
+  ray_backward<kMasked>(st, g, 0.f, white_bg, m_dsig[wv], m_drgb[wv], g_acc);
   wave_sync();
   for (int p = lane; p < N; p += 64) {
     const int src = m_src[wv][p];
@@ -733,64 +390,23 @@ __global__ __launch_bounds__(256) void fine_render_loss_masked_kernel(
 // Forward half of fine_render_loss_kernel (test-time rendering): the same
 // merge, ray_forward and ray_reduce, so the rgb comes out bit for bit as the
 // loss kernel's; plus depth and, when out_acc is given, the weight sum.  No
-// gt, no gradients, no scatter table: an unwritten merged slot (non-finite z)
-// is only ever read, from LDS.
+// gt, no gradients, no source table.
 __global__ __launch_bounds__(256) void composite_fine_fwd_kernel(
     const float* __restrict__ sig_c, const float* __restrict__ rgb_c, const float* __restrict__ zc, int zc_stride,
     int Nc, const float* __restrict__ sig_f, const float* __restrict__ rgb_f, const float* __restrict__ zf, int Nf,
     int R, int white_bg, float* __restrict__ out_rgb, float* __restrict__ out_depth, float* __restrict__ out_acc) {
   __shared__ float m_sig[4][kMaxRaySamples], m_z[4][kMaxRaySamples], m_rgb[4][kMaxRaySamples * 3];
   __shared__ float z_stage[4][kMaxRaySamples];
-  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int wv = threadIdx.x >> 6;
   const int r = blockIdx.x * 4 + wv;
   if (r >= R) return;                       // wave-uniform; only wave-level sync below
-  const int N = Nc + Nf;
-  const float* zcr = zc + (size_t)r * zc_stride;
-  const float* zfr = zf + (size_t)r * Nf;
-  auto wave_sync = [] {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  };
-  float* zs = z_stage[wv];
-  for (int i = lane; i < Nc; i += 64) zs[i] = zcr[i];
-  for (int j = lane; j < Nf; j += 64) zs[Nc + j] = zfr[j];
-  wave_sync();
-  // merged position = own index + number of the other list's samples before it
-  for (int i = lane; i < Nc; i += 64) {
-    const float v = zs[i];
-    int lo = 0, hi = Nf;                    // count zf < v
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (zs[Nc + mid] < v) lo = mid + 1; else hi = mid; }
-    const int p = i + lo;
-    const size_t g = (size_t)r * Nc + i;
-    m_sig[wv][p] = sig_c[g];
-    m_z[wv][p] = v;
-    m_rgb[wv][3 * p + 0] = rgb_c[3 * g + 0];
-    m_rgb[wv][3 * p + 1] = rgb_c[3 * g + 1];
-    m_rgb[wv][3 * p + 2] = rgb_c[3 * g + 2];
-  }
-  for (int j = lane; j < Nf; j += 64) {
-    const float v = zs[Nc + j];
-    int lo = 0, hi = Nc;                    // count zc <= v
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (zs[mid] <= v) lo = mid + 1; else hi = mid; }
-    const int p = j + lo;
-    const size_t g = (size_t)r * Nf + j;
-    m_sig[wv][p] = sig_f[g];
-    m_z[wv][p] = v;
-    m_rgb[wv][3 * p + 0] = rgb_f[3 * g + 0];
-    m_rgb[wv][3 * p + 1] = rgb_f[3 * g + 1];
-    m_rgb[wv][3 * p + 2] = rgb_f[3 * g + 2];
-  }
-  wave_sync();
+  merge_ray<false>(MergePlanes{sig_c, rgb_c, zc, zc_stride, Nc, sig_f, rgb_f, zf, Nf}, r,
+                   MergeRows{m_sig[wv], m_z[wv], m_rgb[wv], nullptr}, z_stage[wv]);
   RayState st;
-  ray_forward(st, m_sig[wv], m_rgb[wv], m_z[wv], N);
+  ray_forward(st, m_sig[wv], m_rgb[wv], m_z[wv], Nc + Nf);
   float o[5];
   ray_reduce(st, o);
-  if (lane == 0) {
-    for (int c = 0; c < 3; ++c) out_rgb[3 * r + c] = white_bg ? fadd_rn(o[c] + 1.f, -o[4]) : o[c];
-    out_depth[r] = o[3];
-    if (out_acc) out_acc[r] = o[4];
-  }
+  store_ray(o, r, white_bg, out_rgb, out_depth, out_acc);
 }
 
 // ---------------------------------------------------------------- misc

@@ -12,7 +12,7 @@
 // contraction; `/` is the correctly rounded division) in the order written, so
 // that tests/scene_util.py restates them bit for bit.  No atomics; every output
 // element is written by exactly one lane.
-#include "cn_common.h"
+#include "cn_ray.h"
 
 namespace cn {
 
@@ -98,10 +98,7 @@ __global__ __launch_bounds__(256) void scene_combine_kernel(const float* __restr
 }
 
 struct SceneCompositeArgs {
-  const float *sig_c, *rgb_c, *zc;      // the combined coarse planes
-  int zc_stride, Nc;
-  const float *sig_f, *rgb_f, *zf;      // the combined fine planes; NULL when Nf == 0
-  int Nf;
+  MergePlanes p;                        // the combined planes; sig_f, rgb_f, zf NULL when Nf == 0
   const float *obj_c, *obj_f;           // [K][R*Nc], [K][R*Nf]; read only with labels
   SceneInvS inv_s;
   int K, R, white_bg;
@@ -111,16 +108,15 @@ struct SceneCompositeArgs {
   int* instance;                        // [R] or NULL, together with obj_acc
 };
 
-// One wave per ray, 4 rays per block, as composite_aov_kernel: the merge of
-// composite_fine_fwd_kernel with the source of every merged slot kept, the
-// unchanged ray_forward / ray_reduce, then per object sum_i w_i f_k,i.
+// One wave per ray, 4 rays per block, as composite_aov_kernel: merge_ray with
+// the source of every merged slot kept, ray_forward / ray_reduce, then per
+// object sum_i w_i f_k,i.
 template <bool kMerge>
 __global__ __launch_bounds__(256) void scene_composite_kernel(SceneCompositeArgs a) {
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + wv;
   if (r >= a.R) return;                     // wave-uniform; only wave-level sync below
-  const int Nc = a.Nc, Nf = a.Nf;
-  const int N = Nc + Nf;
+  const int Nc = a.p.Nc, Nf = a.p.Nf;
   const bool labels = a.obj_acc != nullptr;
   RayState st;
   int src[kMaxPer];                         // coarse i: i, fine j: Nc + j, nothing: -1
@@ -129,63 +125,19 @@ __global__ __launch_bounds__(256) void scene_composite_kernel(SceneCompositeArgs
     __shared__ float m_sig[4][kMaxRaySamples], m_z[4][kMaxRaySamples], m_rgb[4][kMaxRaySamples * 3];
     __shared__ float z_stage[4][kMaxRaySamples];
     __shared__ int m_src[4][kMaxRaySamples];
-    const float* zcr = a.zc + (size_t)r * a.zc_stride;
-    const float* zfr = a.zf + (size_t)r * Nf;
-    auto wave_sync = [] {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-    float* zs = z_stage[wv];
-    for (int i = lane; i < Nc; i += 64) zs[i] = zcr[i];
-    for (int j = lane; j < Nf; j += 64) zs[Nc + j] = zfr[j];
-    // with non-finite z the ranks need not form a permutation: a slot nobody
-    // writes must not name a sample (its index goes to global memory below)
-    for (int p = lane; p < N; p += 64) m_src[wv][p] = -1;
-    wave_sync();
-    // merged position = own index + number of the other list's samples before it
-    for (int i = lane; i < Nc; i += 64) {
-      const float v = zs[i];
-      int lo = 0, hi = Nf;                  // count zf < v
-      while (lo < hi) { const int mid = (lo + hi) >> 1; if (zs[Nc + mid] < v) lo = mid + 1; else hi = mid; }
-      const int p = i + lo;
-      const size_t g = (size_t)r * Nc + i;
-      m_sig[wv][p] = a.sig_c[g];
-      m_z[wv][p] = v;
-      m_rgb[wv][3 * p + 0] = a.rgb_c[3 * g + 0];
-      m_rgb[wv][3 * p + 1] = a.rgb_c[3 * g + 1];
-      m_rgb[wv][3 * p + 2] = a.rgb_c[3 * g + 2];
-      m_src[wv][p] = i;
-    }
-    for (int j = lane; j < Nf; j += 64) {
-      const float v = zs[Nc + j];
-      int lo = 0, hi = Nc;                  // count zc <= v
-      while (lo < hi) { const int mid = (lo + hi) >> 1; if (zs[mid] <= v) lo = mid + 1; else hi = mid; }
-      const int p = j + lo;
-      const size_t g = (size_t)r * Nf + j;
-      m_sig[wv][p] = a.sig_f[g];
-      m_z[wv][p] = v;
-      m_rgb[wv][3 * p + 0] = a.rgb_f[3 * g + 0];
-      m_rgb[wv][3 * p + 1] = a.rgb_f[3 * g + 1];
-      m_rgb[wv][3 * p + 2] = a.rgb_f[3 * g + 2];
-      m_src[wv][p] = Nc + j;
-    }
-    wave_sync();
-    ray_forward(st, m_sig[wv], m_rgb[wv], m_z[wv], N);
+    // the source indexes obj_c / obj_f below
+    merge_ray<true>(a.p, r, MergeRows{m_sig[wv], m_z[wv], m_rgb[wv], m_src[wv]}, z_stage[wv]);
+    ray_forward(st, m_sig[wv], m_rgb[wv], m_z[wv], Nc + Nf);
 #pragma unroll
     for (int k = 0; k < kMaxPer; ++k) src[k] = k < st.cnt ? m_src[wv][st.n0 + k] : -1;
   } else {
-    ray_forward(st, a.sig_c + (size_t)r * Nc, a.rgb_c + (size_t)r * Nc * 3, a.zc + (size_t)r * a.zc_stride, Nc);
+    ray_forward(st, a.p.sig_c + (size_t)r * Nc, a.p.rgb_c + (size_t)r * Nc * 3, a.p.zc + (size_t)r * a.p.zc_stride, Nc);
 #pragma unroll
     for (int k = 0; k < kMaxPer; ++k) src[k] = k < st.cnt ? st.n0 + k : -1;
   }
   float o[5];
   ray_reduce(st, o);
-  if (lane == 0) {
-    for (int c = 0; c < 3; ++c) a.out_rgb[3 * r + c] = a.white_bg ? fadd_rn(o[c] + 1.f, -o[4]) : o[c];
-    a.out_depth[r] = o[3];
-    a.out_acc[r] = o[4];
-  }
+  store_ray(o, r, a.white_bg, a.out_rgb, a.out_depth, a.out_acc);
   if (!labels) return;
   const size_t Mc = (size_t)a.R * Nc, Mf = (size_t)a.R * Nf;
   int best = 0;
@@ -203,9 +155,7 @@ __global__ __launch_bounds__(256) void scene_composite_kernel(SceneCompositeArgs
           part += (double)fmul_rn(st.w[k], scene_share(sk, inv_s, st.sig[k]));
         }
       }
-#pragma unroll
-      for (int k = 32; k > 0; k >>= 1) part += shfl_xor_d(part, k);
-      const float oa = (float)part;
+      const float oa = (float)wave_sum(part);
       if (lane == 0) a.obj_acc[(size_t)r * a.K + ko] = oa;
       if (ko == 0 || oa > best_acc) {       // strictly greater: a tie stays with the lower index
         best = ko;

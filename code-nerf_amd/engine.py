@@ -233,14 +233,18 @@ def composite_bwd(sigma, rgb, z, R, N, grad_rgb, grad_depth=None, white_bg=True)
     return dsig, drgb
 
 
+def _loss_outputs(R, chunk, dev, acc=False):
+    """What a loss entry writes next to the gradients: rgb (R, 3), the per-ray
+    errors (R,), the chunk losses and, for a masked entry, the opacity (R,)."""
+    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    return new(R, 3), new(R), new((R + chunk - 1) // chunk), new(R) if acc else None
+
+
 def render_loss(sigma, rgb, z, R, N, gt, chunk, white_bg=True, dsig=None, drgb=None):
     L = _lib.lib()
     dev = sigma.device
     z_stride = 0 if z.numel() == N else N
-    out_rgb = torch.empty(R, 3, dtype=torch.float32, device=dev)
-    ray_se = torch.empty(R, dtype=torch.float32, device=dev)
-    nchunk = (R + chunk - 1) // chunk
-    chunk_loss = torch.empty(nchunk, dtype=torch.float32, device=dev)
+    out_rgb, ray_se, chunk_loss, _ = _loss_outputs(R, chunk, dev)
     if dsig is None:
         dsig = torch.empty(R * N, dtype=torch.float32, device=dev)
     if drgb is None:
@@ -273,10 +277,7 @@ def render_loss_masked(sigma, rgb, z, R, N, gt, chunk, white_bg=True, dsig=None,
     dev = sigma.device
     sil_coef = _mask_args(ray_weight, acc_target, sil_coef, "render_loss_masked")
     z_stride = 0 if z.numel() == N else N
-    out_rgb = torch.empty(R, 3, dtype=torch.float32, device=dev)
-    ray_se = torch.empty(R, dtype=torch.float32, device=dev)
-    acc = torch.empty(R, dtype=torch.float32, device=dev)
-    chunk_loss = torch.empty((R + chunk - 1) // chunk, dtype=torch.float32, device=dev)
+    out_rgb, ray_se, chunk_loss, acc = _loss_outputs(R, chunk, dev, acc=True)
     if dsig is None:
         dsig = torch.empty(R * N, dtype=torch.float32, device=dev)
     if drgb is None:
@@ -306,9 +307,7 @@ def render_loss_fine(sigma_c, rgb_c, z_c, Nc, sigma_f, rgb_f, z_f, Nf, R, gt, ch
     L = _lib.lib()
     dev = sigma_c.device
     zc_stride = 0 if z_c.numel() == Nc else Nc
-    out_rgb = torch.empty(R, 3, dtype=torch.float32, device=dev)
-    ray_se = torch.empty(R, dtype=torch.float32, device=dev)
-    chunk_loss = torch.empty((R + chunk - 1) // chunk, dtype=torch.float32, device=dev)
+    out_rgb, ray_se, chunk_loss, _ = _loss_outputs(R, chunk, dev)
     check(L.cn_render_loss_fine(ptr(sigma_c), ptr(rgb_c), ptr(z_c), zc_stride, Nc, ptr(sigma_f), ptr(rgb_f),
                                 ptr(z_f), Nf, R, int(white_bg), ptr(gt), chunk, ptr(out_rgb), ptr(ray_se),
                                 ptr(chunk_loss), ptr(dsig_c), ptr(drgb_c), ptr(dsig_f), ptr(drgb_f),
@@ -325,10 +324,7 @@ def render_loss_fine_masked(sigma_c, rgb_c, z_c, Nc, sigma_f, rgb_f, z_f, Nf, R,
     dev = sigma_c.device
     sil_coef = _mask_args(ray_weight, acc_target, sil_coef, "render_loss_fine_masked")
     zc_stride = 0 if z_c.numel() == Nc else Nc
-    out_rgb = torch.empty(R, 3, dtype=torch.float32, device=dev)
-    ray_se = torch.empty(R, dtype=torch.float32, device=dev)
-    acc = torch.empty(R, dtype=torch.float32, device=dev)
-    chunk_loss = torch.empty((R + chunk - 1) // chunk, dtype=torch.float32, device=dev)
+    out_rgb, ray_se, chunk_loss, acc = _loss_outputs(R, chunk, dev, acc=True)
     check(L.cn_render_loss_fine_masked(ptr(sigma_c), ptr(rgb_c), ptr(z_c), zc_stride, Nc, ptr(sigma_f), ptr(rgb_f),
                                        ptr(z_f), Nf, R, int(white_bg), ptr(gt), chunk, ptr(out_rgb), ptr(ray_se),
                                        ptr(chunk_loss), ptr(dsig_c), ptr(drgb_c), ptr(dsig_f), ptr(drgb_f),
